@@ -2,7 +2,13 @@
 """bench.py -- images/sec of DIR.forward (eval, 3 stage outputs) on synthetic 256x256 batches, BASELINE.json config 2
 (batch 64 per GPU, ResNet-50 + init regression + 2 refinement stages, bf16 feature maps / fp32 token+MANO path).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: set up (live autotune, then the faster of the time-tuned and the shipped
+throughput kernel tables on this machine), capture the graphs, warm up, time exactly K steps in one region, optionally write the outputs of
+the last timed step (--dump-outputs DIR: one float32 .npy per output array, see dump_outputs), print the line.  --full adds everything else
+the record carries: the one-in-flight figures, `--repeats` regions (default 5, median reported), reproducibility and parity checks, power,
+roofline and ceiling probes, the other precisions and configurations, the training step and the CPU baselines.
 
 N > 1: one rank per GPU.  Launched by the driver through torch.distributed.run, or -- when WORLD_SIZE is not in the
 environment -- bench.py re-launches ITSELF through torch.distributed.run with N ranks (dir_amd.dist.spawn_ranks); a world size
@@ -44,7 +50,9 @@ def parse_args(argv=None):
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=200)
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--repeats', type=int, default=5, help='timed regions of --steps steps each; the median one is reported')
+    ap.add_argument('--full', action='store_true', help='the whole measurement record (checks, probes, sub-modes, CPU baselines) besides the headline')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR', help='write the outputs of the last timed step to DIR/<name>.npy (float32)')
+    ap.add_argument('--repeats', type=int, default=None, help='timed regions of --steps steps each; the median one is reported (default 1, with --full 5)')
     ap.add_argument('--batch', type=int, default=64, help='images per GPU per step')
     ap.add_argument('--dtype', default='f16', choices=['bf16', 'f16', 'f32'], help="storage of feature maps and convolution weights: bf16 (BASELINE configs[1]), "
                     "f16 = the same data path and MFMA rate on IEEE f16 (11-bit significands: every stage inside 0.01 mm), f32 = exact parity mode")
@@ -74,8 +82,42 @@ def parse_args(argv=None):
     ap.add_argument('--cpu-sample', type=int, default=32, help='images timed on the numpy CPU baseline')
     ap.add_argument('--cpu-threads', type=int, default=16)
     ap.add_argument('--detail-out', default='bench_detail.json', help='the full measurement record (the last stdout line is its compact form)')
-    ap.add_argument('--dump-conv', action='store_true', help='print per-shape timings of every library call (stderr)')
-    return ap.parse_args(argv)
+    ap.add_argument('--dump-conv', action='store_true', help='print per-shape timings of every library call (stderr; --full)')
+    args = ap.parse_args(argv)
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    return args
+
+
+DUMP_SAMPLE = 1 << 19           # elements kept of an output array larger than this (a fixed, seeded sample)
+DUMP_LIMIT = 64 << 20           # bytes written by dump_outputs at most
+
+
+def dump_outputs(outs, path):
+    """Writes what a caller of DirEngine.forward receives -- outs[i] (i = 0..2, one dict per stage) as s<i>.<key>.npy, outs[3] (the seg /
+    dense / proj_feat heads) as <key>.npy -- in float32.  An array of more than DUMP_SAMPLE elements is written as <name>.sample.npy: the
+    elements at DUMP_SAMPLE positions of its flattened C-order (logical) layout, drawn once from numpy's default_rng(0) and sorted, the same
+    positions in every run.  Returns {name: shape written}."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    arrays = [('s%d.%s' % (i, k), v) for i in range(3) for k, v in sorted(outs[i].items())] + sorted(outs[3].items())
+    written, total = {}, 0
+    for name, t in arrays:
+        if t is None:
+            continue
+        n = t.numel()
+        if n > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+            name += '.sample'
+        a = t.float().cpu().numpy()
+        total += a.nbytes
+        if total > DUMP_LIMIT:
+            raise RuntimeError('bench.py: --dump-outputs would write more than %d bytes' % DUMP_LIMIT)
+        np.save(os.path.join(path, name + '.npy'), a)
+        written[name] = list(a.shape)
+    return written
 
 
 def power_probe(step, sync, seconds, steps_per_burst):
@@ -222,7 +264,7 @@ def main():
     sd_np = synth.synth_state_dict(shapes, 1234, cond=args.weights == 'cond')
     sd = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in sd_np.items()}
     gold_name = 'g7c_dir' if args.weights == 'cond' else 'g7_dir'
-    gold = dict(np.load(os.path.join(ROOT, 'tests', 'golden', gold_name + '.npz')))          # the reference's own DIR.forward on these parameters (oracle/gen_golden.py)
+    gold = dict(np.load(os.path.join(ROOT, 'tests', 'golden', gold_name + '.npz'))) if args.full else None   # the reference's own DIR.forward on these parameters (oracle/gen_golden.py)
     GOLD_ROWS = (5, 63)
     tdt = {'bf16': torch.bfloat16, 'f16': torch.float16, 'f32': torch.float32}[args.dtype]
     half = args.dtype in ('bf16', 'f16')
@@ -283,7 +325,7 @@ def main():
     # Two kernel tables, the same bits out of both (checked below): the TIME-tuned one just made serves one forward at a time (latency); the timed
     # graphs take the THROUGHPUT table (dir_amd/tuning/, made by tools/energy_tune.py: fewest joules above idle per launch) when it matches.
     lat_graph, lat_outs, conv_tuning = None, None, 'time (live autotune)' if not args.no_autotune else 'library heuristic'
-    if not args.no_graph and args.inflight > 1:
+    if args.full and not args.no_graph and args.inflight > 1:
         lat_graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(lat_graph):
             lat_outs = fwd()
@@ -307,13 +349,16 @@ def main():
         if meta is not None:
             conv_tuning = 'throughput table dir_amd/tuning/gfx950_%s_b%d_throughput.json (HEAD %s, %d layers differ from the time-tuned choice)' % (
                 tbl_dtype, B, meta.get('head', '?'), meta.get('changed_vs_time_tuned', -1))
+    last = [outs]                                 # the outputs of the latest step (no graph: every eager forward returns its own)
     if args.no_graph:
-        step = fwd
+        def step():
+            last[0] = fwd()
         args.inflight = 1
     elif args.inflight <= 1:
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             outs = fwd()
+        last[0] = outs
         step = graph.replay
     else:
         # steps alternate between `inflight` slots (own stream, graph, synthetic input batch; shared weights): step k's forward
@@ -351,21 +396,23 @@ def main():
 
         def step():
             pipe.launch(counter[0] % args.inflight)
+            last[0] = pipe.outs[counter[0] % args.inflight]
             counter[0] += 1
 
         def one_slot():
             pipe.launch(0)
-        for _ in range(3):
-            one_slot()
-        sync()
-        ser = []
-        for _ in range(3):
-            t0 = time.perf_counter()
-            for _ in range(10):
+        if args.full:
+            for _ in range(3):
                 one_slot()
             sync()
-            ser.append((time.perf_counter() - t0) / 10 * 1e3)
-        serial_tp_ms = statistics.median(ser)   # the timed graphs, one forward at a time
+            ser = []
+            for _ in range(3):
+                t0 = time.perf_counter()
+                for _ in range(10):
+                    one_slot()
+                sync()
+                ser.append((time.perf_counter() - t0) / 10 * 1e3)
+            serial_tp_ms = statistics.median(ser)   # the timed graphs, one forward at a time
 
     if pipe is not None:
         # settle: the table check above rebuilt and released graphs and ran 2 x 60 steps at the package power cap.  VERDICT r5 weak 9: the timed
@@ -382,11 +429,16 @@ def main():
     dt = statistics.median(regions)
     ms_per_step = dt / args.steps * 1e3
     value = world * B * args.steps / dt
-    finite = bool(torch.isfinite(outs[2]['pd_mesh_xyz_left']).all())
+    if args.dump_outputs and rank == 0:
+        # the last timed step's outputs, before anything below replays a graph again (steps cycle through the slots: with the same
+        # arguments the last step always ran the same slot, on the same seeded input batch)
+        dumped = dump_outputs(last[0], args.dump_outputs)
+        sys.stderr.write('bench.py: %d output arrays of the last timed step written to %s\n' % (len(dumped), args.dump_outputs))
+    finite = bool(torch.isfinite(outs[2]['pd_mesh_xyz_left']).all()) if args.full else None
     # overlapped execution must not change results: every slot's outputs from the timed (overlapping) replays against the same
     # slot replayed alone (this is the check that exposed the packed-FP32 hazard)
     reproducible = None
-    if pipe is not None:
+    if args.full and pipe is not None:
         def snap(o):
             return [o[i][k].clone() for i in range(3) for k in ('pd_mesh_xyz_left', 'pd_mesh_xyz_right', 'pd_joint_uv_left', 'pd_offset')] + [o[3]['seg'].clone()]
         for s_ in range(args.inflight):
@@ -400,7 +452,7 @@ def main():
             reproducible = reproducible and all(torch.equal(a, b) for a, b in zip(overlapped[s_], alone))
     # the headline's own parity: slot 0 (it holds `img`, golden rows included) out of an OVERLAPPED round of the timed graphs
     headline_parity = None
-    if rank == 0:
+    if args.full and rank == 0:
         if pipe is not None:
             for s_ in range(args.inflight):
                 pipe.launch(s_)
@@ -420,7 +472,7 @@ def main():
 
     # ---- socket power while the same loop runs (after the timed regions; four forwards in flight sit at the package power cap: DESIGN.md 9)
     power = None
-    if rank == 0 and world == 1 and not args.no_power:
+    if args.full and rank == 0 and world == 1 and not args.no_power:
         power = power_probe(step, sync, 4.0, 50)
         if power is not None and pipe is not None:
             p1 = power_probe(lat_graph.replay if lat_graph is not None else one_slot, sync, 3.0, 20)
@@ -429,7 +481,7 @@ def main():
     # ---- serving variant: the same step without the proj_feat output (335 MB of fp32 per step that apps/eval.py:170-172 never
     #      reads).  Reported beside the headline, never as `value`.
     no_pf = None
-    if rank == 0 and world == 1 and pipe is not None and not args.no_proj_feat_variant:
+    if args.full and rank == 0 and world == 1 and pipe is not None and not args.no_proj_feat_variant:
         pipe2 = E.ForwardPipeline(eng, pipe.imgs, want_proj_feat=False, streams=pipe.streams)      # same hardware queues as the headline pipeline
         c2 = [0]
 
@@ -526,7 +578,7 @@ def main():
                     kernels=kernel_table(recs, reps, dtype_key))
 
 
-    roof = live_roofline(eng, img, args.dtype, ms_per_step) if rank == 0 else None
+    roof = live_roofline(eng, img, args.dtype, ms_per_step) if args.full and rank == 0 else None
     if roof is not None and serial_ms is not None:
         # `all_kernels_ms_per_step` is the SUM of HIP-event brackets around every library call of an EAGER forward (each bracket =
         # the call's kernel(s) + its own dispatch gap on an otherwise idle stream); `ms_per_forward_one_in_flight` is ONE graph replay of the same
@@ -595,7 +647,7 @@ def main():
     #      the headline and again beside it (alternating regions: same clocks): VERDICT r4 item 2 -- "an fp16-storage throughput mode that meets
     #      0.01 mm at every stage at bf16 speed" (tests/test_gpu_dir.py::test_engine_vs_reference_golden_trained_like_weights[f16s])
     other_half = None
-    if rank == 0 and world == 1 and half and pipe is not None and not args.no_other_half:
+    if args.full and rank == 0 and world == 1 and half and pipe is not None and not args.no_other_half:
         odt, oname = (torch.float16, 'f16') if args.dtype == 'bf16' else (torch.bfloat16, 'bf16')
         engo = E.DirEngine(sd, dtype=odt, device=dev)
         engo.forward(img)
@@ -636,7 +688,7 @@ def main():
     #      it saturates, algorithmic bytes = weights once + every layer's activations in and out, beside the counted PMC bytes of the
     #      tracked sweep (profiles/r03_pgcn_batch_sweep_pmc.txt: FETCH_SIZE x 2 + WRITE_SIZE per launch)
     pgcn = None
-    if rank == 0 and world == 1 and half and not args.no_pgcn:
+    if args.full and rank == 0 and world == 1 and half and not args.no_pgcn:
         import ctypes as C
         st3 = eng.stage3
         Lb = _capi.lib()
@@ -671,7 +723,7 @@ def main():
 
     # ---- fp32 exact-parity mode (the mode that meets the 1e-4 mm budget, tests/test_gpu_dir.py): one graph, a few steps
     fp32 = None
-    if rank == 0 and world == 1 and half and not args.no_fp32_mode and not args.no_graph:
+    if args.full and rank == 0 and world == 1 and half and not args.no_fp32_mode and not args.no_graph:
         del pipe
         eng32 = E.DirEngine(sd, dtype=torch.float32, device=dev)
         eng32.forward(img)
@@ -736,7 +788,7 @@ def main():
         return rec
 
     parity, f16m = None, None
-    if rank == 0 and world == 1 and half and not args.no_fp32_mode and not args.no_graph:
+    if args.full and rank == 0 and world == 1 and half and not args.no_fp32_mode and not args.no_graph:
         parity = arith_mode('f16x3', "DirEngine(dtype=float32, arith='f16x3'): fp32 feature maps / token path, every convolution product as three f16 "
                             'MFMAs (hi*hi + lo*hi + hi*lo, fp32 accumulate); meets the 1e-4 mm budget like fp32_mode (8.0e-8 m vs the reference '
                             'golden); roofline priced against the dense f16 peak / 3')
@@ -748,7 +800,7 @@ def main():
     #      over 8), in bf16 and in the arithmetic the config names (fp16 MFMA path: fp32 feature maps, f16 operands); graph + live autotune +
     #      the same forwards in flight as the headline.  No reference counterpart: parity is pinned to the build's oracle.
     cfg5 = None
-    if rank == 0 and world == 1 and half and not args.no_config5 and not args.no_graph:
+    if args.full and rank == 0 and world == 1 and half and not args.no_config5 and not args.no_graph:
         from dir_amd.models.dir import DIR as _DIR
         torch.cuda.empty_cache()
         net5 = _DIR(21, 'x', 0, backbone='hrnet_w48', extra_stages=2)
@@ -804,7 +856,7 @@ def main():
     # ---- training step (BASELINE config 4's per-GPU batch: 32 images, fp32, the whole network: forward in training mode, 42-term
     #      objective, backward, flat gradient bucket, one AdamW launch -- dir_amd/train/step.py); rank 0, single-GPU runs only
     train = None
-    if rank == 0 and world == 1 and half and not args.no_train:
+    if args.full and rank == 0 and world == 1 and half and not args.no_train:
         from dir_amd.optim import FlatAdamW
         from dir_amd.train import step as TSTEP
         torch.cuda.empty_cache()
@@ -879,7 +931,7 @@ def main():
     #   torch_ops   the same graph with its dense operators (99.9 % of the FLOPs) on stock torch CPU kernels (oracle/torch_ops.py),
     #               torch.set_num_threads(os.cpu_count()), at B = 64 and B = 1 -- what the reference itself does on a CPU
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle.dir_forward import dir_forward
         from oracle.torch_ops import stock_torch_dense_ops
         from threadpoolctl import threadpool_limits

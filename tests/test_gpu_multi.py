@@ -78,7 +78,7 @@ def test_bench_multi_rank_code_path_over_gloo(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = tmp_path / 'detail.json'
     env = dict(os.environ, DIR_BENCH_BACKEND='gloo')
-    rc = D.spawn_ranks([os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--repeats', '2', '--no-cpu-baseline', '--no-fp32-mode',
+    rc = D.spawn_ranks([os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--repeats', '2', '--full', '--no-cpu-baseline', '--no-fp32-mode',
                         '--no-train', '--no-proj-feat-variant', '--no-power', '--no-config5', '--no-ceiling-probe', '--no-time-table-pass',
                         '--detail-out', str(out)], 2, env=env, timeout=900)
     assert rc == 0

@@ -10,8 +10,8 @@ echo "pytest -m gpu: $((SECONDS - t0)) s" > $out/durations.txt
 python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.txt 2>&1
 echo "smoke(): rc $? in $((SECONDS - t0)) s (incl. pytest)" >> $out/durations.txt
 t0=$SECONDS
-python bench.py > $out/bench_stdout.txt 2> $out/bench_stderr.txt
-echo "python bench.py (default flags): $((SECONDS - t0)) s" >> $out/durations.txt
+python bench.py --full > $out/bench_stdout.txt 2> $out/bench_stderr.txt
+echo "python bench.py --full: $((SECONDS - t0)) s" >> $out/durations.txt
 tail -1 $out/bench_stdout.txt > $out/bench_line.txt
 cp bench_detail.json $out/bench_detail.json
 TOP=180 python tools/bench_train.py 32 7 2>&1 | grep -v amdgpu.ids > $out/train_step_library_calls.txt

@@ -9,7 +9,7 @@ R=$GRAFT_REPO_ROOT
 out=$R/gpurun_out/$tag
 mkdir -p $out
 rm -f /tmp/dir_autotune.json
-common="--no-cpu-baseline --no-fp32-mode --no-train --no-proj-feat-variant --no-power --no-time-table-pass --force-table --no-config5 --no-ceiling-probe --autotune-cache /tmp/dir_autotune.json"
+common="--full --no-cpu-baseline --no-fp32-mode --no-train --no-proj-feat-variant --no-power --no-time-table-pass --force-table --no-config5 --no-ceiling-probe --autotune-cache /tmp/dir_autotune.json"
 python $R/bench.py --steps 2 --warmup 1 --repeats 1 $common > $out/tune.log 2>&1
 pcmd="python $R/bench.py --no-graph --steps 4 --warmup 2 --repeats 1 $common"
 i=0

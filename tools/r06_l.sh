@@ -3,7 +3,7 @@ R=$GRAFT_REPO_ROOT
 out=$R/gpurun_out/${TAG:-r06_l}
 mkdir -p $out
 cd $R
-common="--steps 100 --repeats 3 --no-cpu-baseline --no-fp32-mode --no-train --no-proj-feat-variant --no-power --no-time-table-pass --no-config5 --no-ceiling-probe --no-other-half --no-pgcn --detail-out /tmp/d.json"
+common="--full --steps 100 --repeats 3 --no-cpu-baseline --no-fp32-mode --no-train --no-proj-feat-variant --no-power --no-time-table-pass --no-config5 --no-ceiling-probe --no-other-half --no-pgcn --detail-out /tmp/d.json"
 for ov in 0 1; do for q in 4 8; do
   DIR_OVERLAP=$ov GPU_MAX_HW_QUEUES=$q timeout 300 python bench.py --inflight 1 $common 2>/dev/null | tail -1 | python -c "
 import sys, json
