@@ -118,7 +118,7 @@ class EvalOutputs(C.Structure):
                                           'root_err')]
 
 
-ABI_VERSION = 37          # DIR_ABI_VERSION (include/dir_hip.h)
+ABI_VERSION = 38          # DIR_ABI_VERSION (include/dir_hip.h)
 DT_F32, DT_BF16, DT_F16X3, DT_F16X1, DT_F16X3P, DT_F16X1P, DT_F16 = 0, 1, 3, 4, 5, 6, 7      # DT_F16: f16 STORAGE (round 5)
 CONV_RELU, CONV_PRE_RELU = 1, 2
 
@@ -243,6 +243,10 @@ _SIGNATURES = {
     'dir_mano_forward': (C.c_int, [C.POINTER(ManoTables), _p, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _i, _p]),
     'dir_jpeg_planes_bytes': (C.c_longlong, [C.c_longlong]),
     'dir_jpeg_decode_records': (C.c_int, [_p, C.c_longlong, _i, _i, _i, _p, C.c_longlong, _p, _p, _p]),
+    'dir_train_noise_field': (C.c_int, [C.c_ulonglong, _p, _i, _p]),
+    'dir_train_augment_images': (C.c_int, [_p, _p, _p, _p, _p, C.c_ulonglong, C.POINTER(C.c_float), C.POINTER(C.c_float), _p, _p, _p, _p, _p,
+                                           _p, _i, _p]),
+    'dir_train_augment_labels': (C.c_int, [_p, C.POINTER(C.c_void_p * 8), _p, C.POINTER(C.c_void_p * 10), _i, _p]),
 }
 
 

@@ -97,6 +97,10 @@ class InterHandSplit(object):
     def img_path(self, idx):
         return os.path.join(self.data_path, self.split, 'img', '%d.jpg' % idx)
 
+    def path(self, kind, idx):
+        """<split>/<kind>/<idx>.jpg: kind 'img', 'mask' or 'dense' (dataset/interhand.py:117-119)"""
+        return os.path.join(self.data_path, self.split, kind, '%d.jpg' % idx)
+
     def frame(self, idx):
         return decode_bgr(self.img_path(idx))
 
@@ -119,7 +123,7 @@ class InterHandSplit(object):
 ANNO_FLOATS = 21 + 2 * 67
 
 
-def _decode_worker(data_path, split, wid, workers, indices, bs, chunk, ready, frames, annos, flags, ctrl, records=False):
+def _decode_worker(data_path, split, wid, workers, indices, bs, chunk, ready, frames, annos, flags, ctrl, records=False, extra=(), extra_frames=()):
     """decode process `wid` of `workers`: owns the chunks t = wid, wid + workers, ... of the flat (batch, chunk) sequence; chunk t of batch b
     goes to rows [k * chunk, ...) of ring slot b % depth once batch b - depth has been released (ctrl[0] = batches released); flags[t] = 1 when
     its frames and annotations are in place (2: failed).  No queue in the steady state: shared-memory words only.
@@ -138,6 +142,7 @@ def _decode_worker(data_path, split, wid, workers, indices, bs, chunk, ready, fr
     if records:
         from .jpeg import file_to_record
     fr, an = [f.numpy() for f in frames], [a.numpy() for a in annos]
+    ex = [[f.numpy() for f in ring] for ring in extra_frames]            # per extra kind: its ring of buffers
     fl, ct = flags.numpy(), ctrl.numpy()
     depth, n, npb = len(fr), len(indices), -(-bs // chunk)
     nb = -(-n // bs)
@@ -162,6 +167,11 @@ def _decode_worker(data_path, split, wid, workers, indices, bs, chunk, ready, fr
                     file_to_record(ds.img_path(indices[lo + j]), fr[slot][j0 + j], IMG_SIZE)
                 else:
                     fr[slot][j0 + j] = ds.frame(indices[lo + j])
+                for kind, ring in zip(extra, ex):
+                    if records:
+                        file_to_record(ds.path(kind, indices[lo + j]), ring[slot][j0 + j], IMG_SIZE)
+                    else:
+                        ring[slot][j0 + j] = decode_bgr(ds.path(kind, indices[lo + j]))
                 an[slot][j0 + j] = ds.anno(indices[lo + j])
             fl[t] = 1
         except Exception:               # noqa: BLE001  (the consumer raises when it sees the flag)
@@ -182,9 +192,12 @@ class DecodeRing(object):
     count (256-thread host: 12 workers 11.7 k images/s, 24: 8.5 k, 96: 3.4 k; with 32-image tasks still 17.1 k at 16 and 6.1 k at 96 --
     profiles/r04_fromdisk_sweep_*.txt).  A batch counts as released when the consumer asks for the next one (it must have finished copying out
     of the buffer by then, as evaluate_from_disk does).  One pass per ring.  The buffers are shared memory registered with the HIP runtime
-    (cudaHostRegister), so the host -> device copy is an asynchronous DMA from where the decoders wrote."""
+    (cudaHostRegister), so the host -> device copy is an asynchronous DMA from where the decoders wrote.
 
-    def __init__(self, data_path, split='test', batch_size=256, workers=8, depth=None, indices=None, pin=True, chunk=32, records=False):
+    extra: names of sibling frame folders decoded next to img/ (dataset/interhand.py:117-119 reads 'mask' and 'dense' for training), in the
+    same form as the img rows (frames or records); the iteration then yields (frames, annos, n, [one buffer per extra name])."""
+
+    def __init__(self, data_path, split='test', batch_size=256, workers=8, depth=None, indices=None, pin=True, chunk=32, records=False, extra=()):
         import torch.multiprocessing as mp
         self.ds = InterHandSplit(data_path, split)
         self.indices = list(range(len(self.ds))) if indices is None else list(indices)
@@ -202,22 +215,28 @@ class DecodeRing(object):
             self.frames = [torch.zeros(batch_size, self.record_bytes, dtype=torch.uint8).share_memory_() for _ in range(depth)]
         else:
             self.frames = [torch.zeros(batch_size, IMG_SIZE, IMG_SIZE, 3, dtype=torch.uint8).share_memory_() for _ in range(depth)]
+        self.extra = tuple(extra)
+        self.extra_frames = [[torch.zeros_like(f).share_memory_() for f in self.frames] for _ in self.extra]
         self.annos = [torch.zeros(batch_size, ANNO_FLOATS, dtype=torch.float32).share_memory_() for _ in range(depth)]
         self.flags = torch.zeros(max(1, len(self) * self.npb), dtype=torch.uint8).share_memory_()
         self.ctrl = torch.zeros(2, dtype=torch.int64).share_memory_()          # [batches released, stop]
         self.pinned = False
         if pin and torch.cuda.is_available():
             rt = torch.cuda.cudart()
-            self.pinned = all(int(rt.cudaHostRegister(t.data_ptr(), t.numel() * t.element_size(), 0)) == 0 for t in self.frames + self.annos)
+            self.pinned = all(int(rt.cudaHostRegister(t.data_ptr(), t.numel() * t.element_size(), 0)) == 0 for t in self._host_buffers())
         ctx = mp.get_context('spawn')
         ready = ctx.Queue()
         self.procs = [ctx.Process(target=_decode_worker, args=(data_path, split, w, self.workers, self.indices, self.bs, self.chunk, ready, self.frames,
-                                                               self.annos, self.flags, self.ctrl, self.records), daemon=True) for w in range(self.workers)]
+                                                               self.annos, self.flags, self.ctrl, self.records, self.extra, self.extra_frames),
+                                 daemon=True) for w in range(self.workers)]
         for p in self.procs:
             p.start()
         for _ in self.procs:             # wait until every decoder is up: a spawned interpreter takes seconds to import
             ready.get(timeout=600)
         self._used = False
+
+    def _host_buffers(self):
+        return self.frames + self.annos + [f for ring in self.extra_frames for f in ring]
 
     def __len__(self):
         return (len(self.indices) + self.bs - 1) // self.bs
@@ -241,7 +260,10 @@ class DecodeRing(object):
             if (mine == 2).any():
                 raise RuntimeError('DecodeRing: a decode worker failed')
             slot = b % self.depth
-            yield self.frames[slot], self.annos[slot], min(self.bs, n_all - b * self.bs)
+            if self.extra:
+                yield self.frames[slot], self.annos[slot], min(self.bs, n_all - b * self.bs), [ring[slot] for ring in self.extra_frames]
+            else:
+                yield self.frames[slot], self.annos[slot], min(self.bs, n_all - b * self.bs)
         ct[0] = nb
 
     def close(self):
@@ -250,7 +272,7 @@ class DecodeRing(object):
             p.join(timeout=10)
         if self.pinned:
             rt = torch.cuda.cudart()
-            for t in self.frames + self.annos:
+            for t in self._host_buffers():
                 rt.cudaHostUnregister(t.data_ptr())
             self.pinned = False
 

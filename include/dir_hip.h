@@ -29,7 +29,7 @@ extern "C" {
 #define DIR_E_LAUNCH (-2)   /* hipLaunchKernel / HIP runtime error          */
 #define DIR_E_NODEVICE (-3) /* no gfx950 device visible                     */
 
-#define DIR_ABI_VERSION 37
+#define DIR_ABI_VERSION 38
 
 int dir_abi_version(void);
 const char* dir_last_error(void);
@@ -937,6 +937,56 @@ int dir_dense_losses_backward(const float* seg_logits, const float* dense_pred, 
 long long dir_jpeg_planes_bytes(long long record_bytes);
 int dir_jpeg_decode_records(const void* records, long long record_stride, int B, int H, int W, void* planes_scratch, long long scratch_bytes, void* out_bgr,
                             int32_t* err_flag, void* stream);
+
+
+/* ---- training input: dataset/interhand.py:__getitem__ of split 'train' (utils/utils.py:202-207, 406-533) for a batch (csrc/augment.hip) ----
+ * Frames are uint8 BGR HWC [B,256,256,3] as dir_jpeg_decode_records writes them; 256 = the reference's img_size.  One dir_aug_params per image,
+ * in DEVICE memory (the host sampler of dir_amd/apps/trainset.py fills them):
+ *   M       get_affine_mat's float32 2x3 matrix (output pixel = M * source pixel of the flipped frame); inverted in double as cv.warpAffine does
+ *   flip    1: the frames are mirrored (img[:, ::-1]) before blur and warp; seg labels 1 / 2 swap; the labels swap left / right and x -> 255 - x
+ *   blur    motion-blur kernel size 1..DIR_AUG_MAX_BLUR (the reference draws 3..9); any other value: no blur
+ *   a, b    add_noise's per-channel gain (channel order B, G, R) and offset, fp64
+ *   kernel  the blur x blur float32 motion-blur kernel, row-major */
+#define DIR_AUG_MAX_BLUR 9
+#define DIR_AUG_MAX_BATCH 4096
+typedef struct dir_aug_params {
+    float M[6];
+    int32_t flip;
+    int32_t blur;
+    double a[3];
+    double b;
+    float kernel[DIR_AUG_MAX_BLUR * DIR_AUG_MAX_BLUR];
+    float pad_[3];
+} dir_aug_params;   /* 400 bytes */
+/* The Gaussian term 255 * N(0, 0.01) of add_noise, float32 [B,256,256,3], element (image b, pixel p = y * 256 + x, channel c):
+ *   h  = splitmix64(splitmix64(seed) + (b * 65536 + p) * 3 + c)        (splitmix64: z += 0x9E3779B97F4A7C15, then the usual two
+ *                                                                        xor-shift-multiply rounds 30 / 0xBF58476D1CE4E5B9, 27 / 0x94D049BB133111EB, 31)
+ *   u1 = ((h >> 41) + 0.5) * 2^-23,  u2 = (h & 0xFFFFFF) * 2^-24
+ *   n  = 2.55f * sqrtf(-2 logf(u1)) * cosf(2 pi u2)                    (Box-Muller, float32)
+ * Deterministic per (seed, b, p, c); dir_train_augment_images with noise = NULL generates exactly this field in-line. */
+int dir_train_noise_field(unsigned long long seed, float* out, int B, void* stream);
+/* The image side, two launches.  (1) filter2D (reflect-101 border, anchor blur / 2) of every img whose params ask for blur, from the flipped
+ * frame into blur_scratch (uint8 [B,256,256,3], caller-owned; rows of other images are not touched): per channel s = 0.f, then
+ * s = s + k[r][q] * src for r, q in row-major order (float32, no fused multiply-add), rounded half to even and clamped (saturate_cast<uchar>).
+ * (2) per output pixel: cv.warpAffine INTER_LINEAR of img (blurred or not) / mask / dense -- inverse in double, coordinates in 10-bit fixed
+ * point rounded to 5 bits, 15-bit weights summing to 32768, a tap outside the frame reads 0, (sum + 2^14) >> 15 --; seg from the warped mask
+ * (hand = G > 50 | R > 50, left = G >= R -> 1, right -> 2, swapped when flipped); add_noise in fp64 (a * v + b + noise, clip 0..255,
+ * truncated to uint8) with `noise` (float32 [B,256,256,3], or NULL: dir_train_noise_field(seed)).  Outputs (fp32):
+ *   img_nchw [B,3,256,256]  RGB / 255, (t - mean) / std of the noised frame (== dir_image_normalize_forward, bit for bit; mean / std host)
+ *   img_rgb  [B,256,256,3]  the noised uint8 BGR frame as float (NULL to skip)      mask_rgb [B,256,256,3] the warped mask (NULL to skip)
+ *   seg      [B,1,256,256]                                                          dense_out [B,3,256,256] the warped dense frame / 255 */
+int dir_train_augment_images(const dir_aug_params* params, const uint8_t* img, const uint8_t* mask, const uint8_t* dense,
+                             const float* noise, unsigned long long seed, const float* mean_host, const float* std_host,
+                             uint8_t* blur_scratch, float* img_nchw, float* img_rgb, float* mask_rgb, float* seg,
+                             float* dense_out, int B, void* stream);
+/* The label side, one launch, fp64 inside, one rounding to fp32 per output.  in_host: 8 device pointers, the gt_batch outputs
+ * joint_xyz L [B,21,3], mesh_xyz L [B,778,3], joint_xyz R, mesh_xyz R (camera space), joint_uv L [B,21,2], mesh_uv L [B,778,2], joint_uv R, mesh_uv R;
+ * camera [B,3,3].  out_host: 10 device pointers, joint_2d L [B,21,3], mesh_2d L [B,778,3], joint_2d R, mesh_2d R, joint_3d L [B,21,3],
+ * mesh_3d L [B,778,3], joint_3d R, mesh_3d R, center L [B,1,3], center R [B,1,3].  With params: the flip (x -> 256 - x - 1, left <-> right),
+ * uv' = M uv, xyz = uvd2xyz_np(uv', z); without (NULL, the val / test splits): xyz and uv as they are.  2D targets = (uv / 256 * 2 - 1, z);
+ * center = joint 9 of the 3D target. */
+int dir_train_augment_labels(const dir_aug_params* params, const float* const* in_host, const float* camera, float* const* out_host,
+                             int B, void* stream);
 
 #ifdef __cplusplus
 }
