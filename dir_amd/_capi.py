@@ -118,7 +118,7 @@ class EvalOutputs(C.Structure):
                                           'root_err')]
 
 
-ABI_VERSION = 38          # DIR_ABI_VERSION (include/dir_hip.h)
+ABI_VERSION = 39          # DIR_ABI_VERSION (include/dir_hip.h)
 DT_F32, DT_BF16, DT_F16X3, DT_F16X1, DT_F16X3P, DT_F16X1P, DT_F16 = 0, 1, 3, 4, 5, 6, 7      # DT_F16: f16 STORAGE (round 5)
 CONV_RELU, CONV_PRE_RELU = 1, 2
 
@@ -247,6 +247,8 @@ _SIGNATURES = {
     'dir_train_augment_images': (C.c_int, [_p, _p, _p, _p, _p, C.c_ulonglong, C.POINTER(C.c_float), C.POINTER(C.c_float), _p, _p, _p, _p, _p,
                                            _p, _i, _p]),
     'dir_train_augment_labels': (C.c_int, [_p, C.POINTER(C.c_void_p * 8), _p, C.POINTER(C.c_void_p * 10), _i, _p]),
+    'dir_render_workspace_bytes': (C.c_longlong, [_i]),
+    'dir_render_two_hands': (C.c_int, [_p, _p, _p, _p, _i, _i, _p, C.c_longlong, _p, _p, _p, _p, _p, _p, _p]),
 }
 
 
@@ -258,7 +260,7 @@ PROFILE = None
 _pending = {}
 _NO_PROFILE = ('dir_conv2d_as_supported', 'dir_abi_version', 'dir_bn_one_launch_status', 'dir_bn_one_launch_enable', 'dir_last_error', 'dir_device_info', 'dir_launch_log_reset', 'dir_launch_log_get', 'dir_launch_log_note',
                'dir_bone_fusion_scratch_bytes', 'dir_dense_losses_workspace_bytes', 'dir_dense_losses_backward_workspace_bytes',
-               'dir_gemm_f32_splitk_workspace_bytes', 'dir_bn_train_workspace_bytes', 'dir_bn_sync_workspace_bytes', 'dir_bn_frozen_workspace_bytes', 'dir_jpeg_planes_bytes', 'dir_colsum_workspace_bytes', 'dir_conv2d_wgrad_workspace_bytes', 'dir_conv2d_wgrad_f16x3_workspace_bytes')
+               'dir_gemm_f32_splitk_workspace_bytes', 'dir_bn_train_workspace_bytes', 'dir_bn_sync_workspace_bytes', 'dir_bn_frozen_workspace_bytes', 'dir_jpeg_planes_bytes', 'dir_render_workspace_bytes', 'dir_colsum_workspace_bytes', 'dir_conv2d_wgrad_workspace_bytes', 'dir_conv2d_wgrad_f16x3_workspace_bytes')
 
 
 def annotate(**kw):

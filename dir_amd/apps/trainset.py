@@ -6,7 +6,8 @@
   augment_batch     uint8 img / mask / dense frames + GT -> the reference's (inputs, targets, meta_info) dicts, three launches
                     (dir_train_augment_images: blur pre-pass + image pass; dir_train_augment_labels)
   TrainBatches      DataLoader(InterHandDataset(data_path, 'train'), shuffle=True, drop_last=True) of train.py:64-70: DecodeRing carries
-                    img / mask / dense, gt_batch runs the GT MANO, augment_batch the rest
+                    img / mask / dense (or img only, with dense_color: mask / dense rendered from gt_batch's meshes by
+                    dir_amd.utils.vis_utils), gt_batch runs the GT MANO, augment_batch the rest
 
 Matching the reference's random STREAM is not a goal (its DataLoader workers seed themselves); the distributions are the reference's.  The
 Gaussian term of add_noise comes from a counter RNG on the GPU (dir_train_noise_field, include/dir_hip.h), float32 instead of float64 draws.
@@ -198,9 +199,16 @@ class TrainBatches(object):
     mano_layer: the GT MANO layers ({'left', 'right'}, dataset.gt_layers_from_checkpoint).  augment=False (val / test): no flip, blur or
     warp, but the noise is applied, as the reference does.  Decode: `workers` processes of a DecodeRing carry img / mask / dense
     (records=True: the Huffman decode only, the rest of the JPEG decode on the GPU).  The parameter draws of every batch are kept in
-    `self.last_params` (numpy dir_aug_params) and the noise seed in `self.last_seed`."""
+    `self.last_params` (numpy dir_aug_params) and the noise seed in `self.last_seed`.
 
-    def __init__(self, data_path, mano_layer, split='train', batch_size=32, workers=8, seed=0, augment=True, records=True, device='cuda'):
+    dense_color: the dense colour table (the [778,3] array in 0..1 of get_dense_color_path(), or the pickle's path).  Given, mask and
+    dense are not read from files: they are rendered per batch (csrc/render.hip, render_data's rules) from the camera-frame vertices of
+    gt_batch, whose tuple augment_batch then reuses, so the ground-truth MANO runs once; only img/ is decoded.  These frames are the
+    arrays cv.imwrite would receive, without the JPEG round trip the files have been through, so they are not the file path's bytes.
+    The faces are the right GT layer's (ManoLayer.get_faces()); a layer without faces (a checkpoint without th_faces) is an error."""
+
+    def __init__(self, data_path, mano_layer, split='train', batch_size=32, workers=8, seed=0, augment=True, records=True, device='cuda',
+                 dense_color=None):
         from .dataset import InterHandSplit
         self.data_path, self.split, self.mano_layer = data_path, split, mano_layer
         self.bs, self.workers, self.augment, self.records = batch_size, workers, augment, records
@@ -209,6 +217,12 @@ class TrainBatches(object):
         self.n = len(InterHandSplit(data_path, split))
         self.epoch = 0
         self.last_params, self.last_seed = None, None
+        self.render = None
+        if dense_color is not None:
+            from ..utils import vis_utils as V
+            self.render = (torch.from_numpy(V.faces_from_layers(mano_layer)).to(self.device),
+                           torch.from_numpy(V.load_dense_colors(dense_color)).to(self.device),
+                           torch.empty(int(_capi.lib().dir_render_workspace_bytes(batch_size)), dtype=torch.uint8, device=self.device))
 
     def __len__(self):
         return self.n // self.bs
@@ -219,22 +233,24 @@ class TrainBatches(object):
         self.epoch += 1
         if len(perm) == 0:
             return
+        nf = 1 if self.render is not None else 3                          # frames decoded per sample: img (+ mask, dense)
         ring = DecodeRing(self.data_path, self.split, self.bs, workers=self.workers, indices=perm.tolist(), records=self.records,
-                          extra=('mask', 'dense'))
+                          extra=('mask', 'dense') if nf == 3 else ())
         dev, bs = self.device, self.bs
         copy_stream = torch.cuda.Stream(dev)
         dec = None
         if self.records:
             from .jpeg import RecordDecoder
-            dec = RecordDecoder(3 * bs, ring.record_bytes, S, dev)
+            dec = RecordDecoder(nf * bs, ring.record_bytes, S, dev)
         try:
-            for frames, annos, n, (masks, dense) in ring:
+            for item in ring:
+                frames, annos = item[0], item[1]
                 params = sample_params(self.rng, bs, self.augment)
                 seed = int(self.rng.integers(0, 2 ** 63))
                 main = torch.cuda.current_stream(dev)
                 with torch.cuda.stream(copy_stream):
-                    host = [frames, masks, dense]
-                    raw = torch.empty((3 * bs,) + tuple(frames.shape[1:]), dtype=torch.uint8, device=dev)
+                    host = [frames] + (list(item[3]) if nf == 3 else [])
+                    raw = torch.empty((nf * bs,) + tuple(frames.shape[1:]), dtype=torch.uint8, device=dev)
                     for j, h in enumerate(host):
                         raw[j * bs:(j + 1) * bs].copy_(h, non_blocking=True)
                     an = annos.to(dev, non_blocking=True)
@@ -246,12 +262,21 @@ class TrainBatches(object):
                 for t in (raw, an, pr):
                     t.record_stream(main)
                 if dec is not None:
-                    fr = torch.empty(3 * bs, S, S, 3, dtype=torch.uint8, device=dev)
+                    fr = torch.empty(nf * bs, S, S, 3, dtype=torch.uint8, device=dev)
                     dec(raw, fr)
                 else:
                     fr = raw
                 self.last_params, self.last_seed = params, seed
-                yield augment_batch(fr[:bs], fr[bs:2 * bs], fr[2 * bs:], an, pr, mano_layer=self.mano_layer, seed=seed, augment=self.augment)
+                if self.render is None:
+                    yield augment_batch(fr[:bs], fr[bs:2 * bs], fr[2 * bs:], an, pr, mano_layer=self.mano_layer, seed=seed, augment=self.augment)
+                    continue
+                from ..utils.vis_utils import render_frames
+                from .dataset import gt_batch
+                gt = gt_batch(self.mano_layer, an)
+                faces, colors, ws = self.render
+                verts = torch.cat((gt[1], gt[3]), dim=1).contiguous()
+                masks, dense = render_frames(verts, faces, gt[8], colors, S, workspace=ws)
+                yield augment_batch(fr, masks, dense, gt, pr, seed=seed, augment=self.augment)
             if dec is not None:
                 dec.check()                                                # a record that was not a 256x256 image would have left its frame stale
         finally:

@@ -29,7 +29,7 @@ extern "C" {
 #define DIR_E_LAUNCH (-2)   /* hipLaunchKernel / HIP runtime error          */
 #define DIR_E_NODEVICE (-3) /* no gfx950 device visible                     */
 
-#define DIR_ABI_VERSION 38
+#define DIR_ABI_VERSION 39
 
 int dir_abi_version(void);
 const char* dir_last_error(void);
@@ -987,6 +987,31 @@ int dir_train_augment_images(const dir_aug_params* params, const uint8_t* img, c
  * center = joint 9 of the 3D target. */
 int dir_train_augment_labels(const dir_aug_params* params, const float* const* in_host, const float* camera, float* const* out_host,
                              int B, void* stream);
+
+/* ---- two-hand mesh rasteriser: dataset/prepare_data.py:174-214 (render_data) through mano_two_hands_renderer (csrc/render.hip) ----
+ * The rules (pytorch3d's rasterize_meshes with blur_radius 0, faces_per_pixel 1, perspective-correct barycentrics, no culling, no z
+ * clipping; HardPhongShader + AmbientLights) are written out in the header comment of csrc/render.hip.  Device pointers:
+ *   verts   float32 [B,1556,3] camera frame, left hand 0..777, right 778..1555
+ *   faces   int32 [3076,3]: left = right faces with columns [1,0,2], right = right faces + 778 (an index outside 0..1555 skips the face)
+ *   K       float32 [B,3,3] intrinsics of the S x S image
+ *   colors  float32 [1556,3] per-vertex colour table (0..255 scale), needed by color_u8 / color_f32 only
+ * Outputs, each written when its pointer is not NULL (at least one):
+ *   pix_to_face  int32 [B,S,S]      face index within the mesh (0..3075), -1 background
+ *   zbuf         float32 [B,S,S]    view-space depth of the face, -1 background
+ *   bary         float32 [B,S,S,3]  perspective-correct barycentrics, -1 background
+ *   mask         uint8 [B,S,S,3]    the mask frame cv.imwrite receives (left (0,0,255), right (0,255,0), background 1)
+ *   color_u8     uint8 [B,S,S,3]    the frame of `colors` cv.imwrite receives (background 1)
+ *   color_f32    float32 [B,S,S,3]  texel / 255 of `colors` (the renderer's image; background 1/255)
+ * workspace: dir_render_workspace_bytes(B) bytes of device memory (per-face tile ranges).  S in 16..1024. */
+#define DIR_RENDER_VERTS 1556
+#define DIR_RENDER_FACES 3076
+#define DIR_RENDER_MIN_SIZE 16
+#define DIR_RENDER_MAX_SIZE 1024
+#define DIR_RENDER_MAX_BATCH 4096
+long long dir_render_workspace_bytes(int B);
+int dir_render_two_hands(const float* verts, const int32_t* faces, const float* K, const float* colors, int B, int S, void* workspace,
+                         long long workspace_bytes, int32_t* pix_to_face, float* zbuf, float* bary, uint8_t* mask, uint8_t* color_u8,
+                         float* color_f32, void* stream);
 
 #ifdef __cplusplus
 }

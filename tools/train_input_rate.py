@@ -1,7 +1,9 @@
 """Rate of the training input: TrainBatches over a synthetic train split (tests/helpers/fake_train_split.py's layout), images/s, and the
 GPU time of the augmentation launches alone (HIP events around augment_batch on decoded frames).
 
-  python tools/train_input_rate.py [--n 512] [--bs 32] [--workers 8] [--records 1] [--out FILE]"""
+  python tools/train_input_rate.py [--n 512] [--bs 32] [--workers 8] [--records 1] [--dense_color 0] [--out FILE]
+
+--dense_color 1: mask / dense rendered on the GPU from the GT meshes (TrainBatches(dense_color=...)) instead of decoded from files."""
 import argparse
 import json
 import os
@@ -22,6 +24,7 @@ def main():
     ap.add_argument('--bs', type=int, default=32)
     ap.add_argument('--workers', type=int, default=8)
     ap.add_argument('--records', type=int, default=1)
+    ap.add_argument('--dense_color', type=int, default=0)
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     from fake_train_split import write_train_split
@@ -60,7 +63,8 @@ def main():
         t0 = time.perf_counter()
         write_train_split(d, a.n, seed=0)
         res['write_split_s'] = time.perf_counter() - t0
-        tb = T.TrainBatches(d, mano, 'train', batch_size=a.bs, workers=a.workers, seed=0, records=bool(a.records))
+        table = np.random.default_rng(0).random((778, 3)) if a.dense_color else None
+        tb = T.TrainBatches(d, mano, 'train', batch_size=a.bs, workers=a.workers, seed=0, records=bool(a.records), dense_color=table)
         for _ in tb:                                              # first epoch: spawn + warm-up
             pass
         torch.cuda.synchronize()
@@ -73,7 +77,7 @@ def main():
             k += inputs['img'].shape[0]
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-    res.update(images=k, seconds=dt, images_per_sec=k / dt, workers=a.workers, records=bool(a.records),
+    res.update(images=k, seconds=dt, images_per_sec=k / dt, workers=a.workers, records=bool(a.records), dense_color=bool(a.dense_color),
                epoch_start_s=t0 - t_start, note='second epoch after its first batch (the decode processes of the epoch are up)')
     line = json.dumps(res)
     print(line)
