@@ -954,10 +954,48 @@ class ResidualOp(object):
         self.c1.link_split(self.c2)
         if self.dual is None:
             self.c2.link_split(self.c3)
+        # the whole block as ONE launch (dir_residual_chain_forward) where the library has the shape: the three weight matrices as the kernel's
+        # fragment streams, packed here once (eagerly: nothing is allocated or copied on the first call, which may be under graph capture)
+        self.chain = None
+        self.cout, self.cin, self.kh, self.kw, self.stride = self.c3.cout, self.c1.cin, 3, 3, 1      # what autotune / export_tuning read from a conv op
+        self.variant = {}                                     # (a single kernel: every variant code is a no-op, as for BneckChainOp)
+        if (self.res_chain and dtype in HALF and self.dual is not None and self.dual.w_stream is not None
+                and _capi.lib().dir_residual_chain_supported(_dt(dtype), self.c1.cin, self.c1.cout, self.dual.cout, 1, 32, 32, self.c1.cin, 0, self.dual.cout, 0)):
+            self.chain_w = (pack_as_weights(self.c1.w, 1), pack_as_weights(self.c2.w, 1),
+                            pack_as_weights(self.dual.w.reshape(self.dual.cout, 1, 1, self.dual.cin + self.dual.cin2), 1))
+            self.chain = _capi.ResChainParams(*([_capi.ptr(t) for t in self.chain_w] + [_capi.ptr(t) for t in (
+                self.c1.pre_scale, self.c1.pre_shift, self.c1.scale, self.c1.shift, self.c2.scale, self.c2.shift, self.dual.shift)]
+                + [self.c1.cin, self.c1.cout, self.dual.cout, _dt(dtype)]))
 
     fold_skip = os.environ.get('DIR_FOLD_SKIP', '1') != '0'
+    res_chain = os.environ.get('DIR_RES_CHAIN', '1') != '0'        # 16-bit storage, 512 -> 128 -> 256 blocks on 32x32 / 16x16 maps: one launch per block
+
+    def _chain_call(self, x, out=None, out_coff=0):
+        """the fused launch, or None when the library does not take these shapes (the caller runs the three launches)"""
+        B, H, W, cbuf = x.shape
+        cs = out.shape[3] if out is not None else self.cout
+        if x.dtype != self.c1.dtype or (out is not None and out.dtype != x.dtype) or not x.is_contiguous() or (out is not None and not out.is_contiguous()):
+            return None
+        if not _capi.lib().dir_residual_chain_supported(_dt(x.dtype), self.cin, self.c1.cout, self.cout, B, H, W, cbuf, 0, cs, out_coff):
+            return None
+        if out is None:
+            out = torch.empty(B, H, W, self.cout, device=x.device, dtype=x.dtype)
+        if getattr(_TLS, 'capture', None) is not None:       # autotune_energy: this call, replayable
+            _TLS.capture.append((self, (x,), dict(out=out, out_coff=out_coff)))
+        if _capi.PROFILE is not None:
+            m, mid = B * H * W, self.c1.cout
+            _capi.annotate(family='conv', flops=2.0 * m * (mid * self.cin + mid * 9 * mid + self.cout * (mid + self.cin)), op=self, dtype='bf16',
+                           shape='M=%d residual 1x1(%d->%d)+3x3+1x1(->%d)+skip' % (m, self.cin, mid, self.cout),
+                           bytes=(m * (self.cin + self.cout) + self.c1.w.numel() + self.c2.w.numel() + self.dual.w.numel()) * 2)
+        _capi.check(_capi.lib().dir_residual_chain_forward(C.byref(self.chain), _capi.ptr(x), _capi.ptr(out), B, H, W, cbuf, 0, cs, out_coff,
+                                                           _capi.stream_ptr()), 'dir_residual_chain_forward')
+        return out
 
     def __call__(self, x, out=None, out_coff=0):
+        if self.chain is not None and self.res_chain:
+            y = self._chain_call(x, out, out_coff)
+            if y is not None:
+                return y
         if self.dual is not None:
             return self.dual(self.c2(self.c1(x)), x, out=out, out_coff=out_coff)
         res = self.skip(x) if self.need_skip else x

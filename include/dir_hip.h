@@ -29,7 +29,7 @@ extern "C" {
 #define DIR_E_LAUNCH (-2)   /* hipLaunchKernel / HIP runtime error          */
 #define DIR_E_NODEVICE (-3) /* no gfx950 device visible                     */
 
-#define DIR_ABI_VERSION 39
+#define DIR_ABI_VERSION 40
 
 int dir_abi_version(void);
 const char* dir_last_error(void);
@@ -864,6 +864,36 @@ typedef struct dir_bneck_tail_params {
 } dir_bneck_tail_params;
 int dir_bottleneck_tail_forward(const dir_bneck_tail_params* p, const void* y2, const void* residual, void* out, void* y1_next,
                                 long long M, void* stream);
+
+/* a1, decoder: one hourglass Residual block with a projection skip in ONE launch (csrc/res_chain.hip)
+ *   models/backbone/hourglass.py:33-70   out = conv3(relu(bn3(conv2(relu(bn2(conv1(relu(bn1(x)))))))) + skip_layer(x)
+ * for the shape four of the decoder's six blocks have: Cin = 512, Cmid = 128, Cout = 256, stride 1, on 32x32 or 16x16 maps, 16-bit storage
+ * (DIR_DT_BF16 | DIR_DT_F16).  x is NHWC [B,H,W,in_cstride] read from channel in_coff; out is NHWC [B,H,W,out_cstride] written at channels
+ * [out_coff, out_coff + 256), every other channel of the buffer is left alone.  y1 and y2 stay on the CU.  Same fp32 accumulation chains and
+ * rounding points (y1, y2 and out rounded to the storage kind) as dir_conv2d_forward (conv1 with the pre-activation) -> dir_conv2d_forward
+ * (conv2) -> dir_conv2d_dual_forward (conv3 + skip_layer): the output is bit-identical to those three launches.
+ * w1 / w2 / w3: the three weight matrices as MFMA A-operand fragments in the order the kernel's waves consume them, the layout of
+ * dir_conv2d_as_forward's weight stream with one 32-channel block per wave (dir_amd/engine.py::pack_as_weights(w, 1)):
+ *   [Cout / 128][4][steps][4 k-steps][64 lanes][8], step = (64-channel slab) * (kh kw) + tap; lane l of k-step ks holds
+ *   W[32 * block + (l & 31)][tap * Cin + 64 * slab + 8 * ks + 32 * (l >> 5) .. + 8]
+ * from conv1.weight [128][512], conv2.weight [128][3][3][128] and [conv3.weight | skip_layer.weight] [256][128 + 512].
+ * pre_scale / pre_shift [512]: bn1 folded; scale1 / shift1 [128]: bn2 (+ conv1 bias) folded; scale2 / shift2 [128]: bn3 (+ conv2 bias);
+ * shift3 [256]: conv3 bias + skip_layer bias.  fp32 device pointers.
+ * dir_residual_chain_supported: 1 if the forward call takes these shapes, else 0 (the caller then runs the three launches); no launch.
+ * dir_residual_chain_forward returns DIR_E_INVALID for anything dir_residual_chain_supported rejects. */
+typedef struct dir_res_chain_params {
+    const void* w1; const void* w2; const void* w3;
+    const float* pre_scale; const float* pre_shift;
+    const float* scale1; const float* shift1;
+    const float* scale2; const float* shift2;
+    const float* shift3;
+    int32_t Cin, Cmid, Cout;   /* 512, 128, 256 */
+    int32_t dtype;             /* DIR_DT_BF16 | DIR_DT_F16: storage kind of x, out and the weight streams */
+} dir_res_chain_params;
+int dir_residual_chain_supported(int dtype, int Cin, int Cmid, int Cout, int B, int H, int W, int in_cstride, int in_coff, int out_cstride,
+                                 int out_coff);
+int dir_residual_chain_forward(const dir_res_chain_params* p, const void* x, void* out, int B, int H, int W, int in_cstride, int in_coff,
+                               int out_cstride, int out_coff, void* stream);
 
 /* a13 / 8f rank 2, forward half: the training objective, models/dir.py:542-594 (SmoothL1Loss models/loss.py:63-93, EdgeLengthLoss
  * :36-60, NormalVectorLoss :6-33, nn.CrossEntropyLoss(weight), lovasz_softmax models/lovasz_loss.py:155-202).  Forward values;
