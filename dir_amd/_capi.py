@@ -123,7 +123,12 @@ class EvalOutputs(C.Structure):
                                           'root_err')]
 
 
-ABI_VERSION = 40          # DIR_ABI_VERSION (include/dir_hip.h)
+class RenderLights(C.Structure):         # dir_render_lights
+    _fields_ = [('ambient', C.c_float * 3), ('diffuse', C.c_float * 3), ('specular', C.c_float * 3), ('location', C.c_float * 3),
+                ('shininess', C.c_float)]
+
+
+ABI_VERSION = 41          # DIR_ABI_VERSION (include/dir_hip.h)
 DT_F32, DT_BF16, DT_F16X3, DT_F16X1, DT_F16X3P, DT_F16X1P, DT_F16 = 0, 1, 3, 4, 5, 6, 7      # DT_F16: f16 STORAGE (round 5)
 CONV_RELU, CONV_PRE_RELU = 1, 2
 
@@ -256,6 +261,12 @@ _SIGNATURES = {
     'dir_train_augment_labels': (C.c_int, [_p, C.POINTER(C.c_void_p * 8), _p, C.POINTER(C.c_void_p * 10), _i, _p]),
     'dir_render_workspace_bytes': (C.c_longlong, [_i]),
     'dir_render_two_hands': (C.c_int, [_p, _p, _p, _p, _i, _i, _p, C.c_longlong, _p, _p, _p, _p, _p, _p, _p]),
+    'dir_render_adjacency_bytes': (C.c_longlong, []),
+    'dir_render_adjacency': (C.c_int, [_p, _p, C.c_longlong, _p]),
+    'dir_render_vertex_normals': (C.c_int, [_p, _p, _p, _i, _p, _p]),
+    'dir_render_shaded_workspace_bytes': (C.c_longlong, [_i]),
+    'dir_render_joints': (C.c_int, [_p, _p, _p, _i, _i, C.c_float, C.c_float, _p]),
+    'dir_render_shaded': (C.c_int, [_p, _p, _p, _p, _p, _p, _p, C.POINTER(RenderLights), _p, _i, _i, _p, C.c_longlong, _p, _p, _p, _p, _p, _p]),
 }
 
 
@@ -267,7 +278,7 @@ PROFILE = None
 _pending = {}
 _NO_PROFILE = ('dir_conv2d_as_supported', 'dir_residual_chain_supported', 'dir_abi_version', 'dir_bn_one_launch_status', 'dir_bn_one_launch_enable', 'dir_last_error', 'dir_device_info', 'dir_launch_log_reset', 'dir_launch_log_get', 'dir_launch_log_note',
                'dir_bone_fusion_scratch_bytes', 'dir_dense_losses_workspace_bytes', 'dir_dense_losses_backward_workspace_bytes',
-               'dir_gemm_f32_splitk_workspace_bytes', 'dir_bn_train_workspace_bytes', 'dir_bn_sync_workspace_bytes', 'dir_bn_frozen_workspace_bytes', 'dir_jpeg_planes_bytes', 'dir_render_workspace_bytes', 'dir_colsum_workspace_bytes', 'dir_conv2d_wgrad_workspace_bytes', 'dir_conv2d_wgrad_f16x3_workspace_bytes')
+               'dir_gemm_f32_splitk_workspace_bytes', 'dir_bn_train_workspace_bytes', 'dir_bn_sync_workspace_bytes', 'dir_bn_frozen_workspace_bytes', 'dir_jpeg_planes_bytes', 'dir_render_workspace_bytes', 'dir_render_adjacency_bytes', 'dir_render_shaded_workspace_bytes', 'dir_colsum_workspace_bytes', 'dir_conv2d_wgrad_workspace_bytes', 'dir_conv2d_wgrad_f16x3_workspace_bytes')
 
 
 def annotate(**kw):

@@ -29,7 +29,7 @@ extern "C" {
 #define DIR_E_LAUNCH (-2)   /* hipLaunchKernel / HIP runtime error          */
 #define DIR_E_NODEVICE (-3) /* no gfx950 device visible                     */
 
-#define DIR_ABI_VERSION 40
+#define DIR_ABI_VERSION 41
 
 int dir_abi_version(void);
 const char* dir_last_error(void);
@@ -1042,6 +1042,43 @@ long long dir_render_workspace_bytes(int B);
 int dir_render_two_hands(const float* verts, const int32_t* faces, const float* K, const float* colors, int B, int S, void* workspace,
                          long long workspace_bytes, int32_t* pix_to_face, float* zbuf, float* bary, uint8_t* mask, uint8_t* color_u8,
                          float* color_f32, void* stream);
+
+/* ---- shaded and orthographic rendering of the same two-hand mesh: mano_two_hands_renderer.render_rgb / render_rgb_orth and the
+ * scale= / trans2d= cameras (utils/vis_utils.py:138-149, 278-330; HardPhongShader with PointLights, default Materials / BlendParams).
+ * The rules are written out in the header comment of csrc/render.hip.  Device pointers unless said otherwise:
+ *   adjacency  dir_render_adjacency_bytes() bytes, made once per face table by dir_render_adjacency: for every vertex its incident
+ *              (face, corner) pairs in ascending face index, so that the vertex normals are summed in a fixed order
+ *   normals    float32 [B,1556,3] vertex normals in world space (pytorch3d's verts_normals_packed)
+ *   K          float32 [B,3,3], the perspective camera; OR
+ *   scale      float32 [B] and trans2d float32 [B,2], the orthographic camera (focal 2 scale, principal point -trans2d,
+ *              R = diag(-1,-1,1), T = (0,0,10)).  Exactly one camera kind is given; the other kind's pointers are NULL.
+ *   colors     float32 [1556,3] vertex colours (0..255), lights: HOST pointer; both needed by shaded_f32 / overlay_u8, as is adjacency
+ *   background uint8 [B,S,S,3] or NULL: the frame that shows through where no face covers the pixel (overlay_u8 only)
+ * Outputs, each written when its pointer is not NULL (at least one): pix_to_face / zbuf / bary as dir_render_two_hands (under the
+ * orthographic camera zbuf is z + 10 and bary are the plain screen-space barycentrics),
+ *   shaded_f32  float32 [B,S,S,3]  colour / 255, background 1/255
+ *   overlay_u8  uint8 [B,S,S,3]    round_half_even(clamp(fl32(colour / 255) * 255, 0, 255)) where a face covers the pixel, else the
+ *                                  background frame's bytes (1 without a frame)
+ * workspace: dir_render_shaded_workspace_bytes(B) bytes (tile ranges + vertex normals).  shininess must be 64. */
+typedef struct dir_render_lights {
+    float ambient[3], diffuse[3], specular[3];      /* light colour x material colour per channel (the default Materials are 1) */
+    float location[3];                              /* the point light, world space */
+    float shininess;                                /* 64: the power is taken as six successive squarings */
+} dir_render_lights;
+long long dir_render_adjacency_bytes(void);
+int dir_render_adjacency(const int32_t* faces, void* adjacency, long long adjacency_bytes, void* stream);
+int dir_render_vertex_normals(const float* verts, const int32_t* faces, const void* adjacency, int B, float* normals, void* stream);
+long long dir_render_shaded_workspace_bytes(int B);
+int dir_render_shaded(const float* verts, const int32_t* faces, const void* adjacency, const float* K, const float* scale,
+                      const float* trans2d, const float* colors, const dir_render_lights* lights, const uint8_t* background, int B, int S,
+                      void* workspace, long long workspace_bytes, int32_t* pix_to_face, float* zbuf, float* bary, float* shaded_f32,
+                      uint8_t* overlay_u8, void* stream);
+
+/* Predicted 2-D joints drawn over a picture, in place: image uint8 [B,S,S,3], uv_left / uv_right float32 [B,21,2] in -1..1 (pd_joint_uv_*;
+ * joint 0 the wrist, then four joints per finger, thumb first).  Discs of joint_radius pixels and bones of half-width bone_radius, by this
+ * project's own coverage rule and palette (csrc/render.hip) -- it is NOT OpenCV's drawing. */
+int dir_render_joints(uint8_t* image, const float* uv_left, const float* uv_right, int B, int S, float joint_radius, float bone_radius,
+                      void* stream);
 
 #ifdef __cplusplus
 }
