@@ -123,12 +123,17 @@ class EvalOutputs(C.Structure):
                                           'root_err')]
 
 
+class ValMetricsDesc(C.Structure):        # dir_val_metrics_desc
+    _fields_ = [('joints_pd', (C.c_void_p * 2) * 8), ('verts_pd', (C.c_void_p * 2) * 8), ('joints_gt', C.c_void_p * 2),
+                ('verts_gt', C.c_void_p * 2), ('sample_sums', C.c_void_p), ('acc', C.c_void_p), ('batches', C.c_void_p)]
+
+
 class RenderLights(C.Structure):         # dir_render_lights
     _fields_ = [('ambient', C.c_float * 3), ('diffuse', C.c_float * 3), ('specular', C.c_float * 3), ('location', C.c_float * 3),
                 ('shininess', C.c_float)]
 
 
-ABI_VERSION = 41          # DIR_ABI_VERSION (include/dir_hip.h)
+ABI_VERSION = 42          # DIR_ABI_VERSION (include/dir_hip.h)
 DT_F32, DT_BF16, DT_F16X3, DT_F16X1, DT_F16X3P, DT_F16X1P, DT_F16 = 0, 1, 3, 4, 5, 6, 7      # DT_F16: f16 STORAGE (round 5)
 CONV_RELU, CONV_PRE_RELU = 1, 2
 
@@ -198,6 +203,7 @@ _SIGNATURES = {
     'dir_gt_mano_forward': (C.c_int, [C.POINTER(ManoTables), _p, _p, _i, _p, _p, _p, _i, _i, _p, _p, _i, _p]),
     'dir_joint_regress_forward': (C.c_int, [_p, _p, _p, _i, _p]),
     'dir_eval_metrics_forward': (C.c_int, [C.POINTER(EvalInputs), C.POINTER(EvalOutputs), _i, _i, _i, _p]),
+    'dir_val_metrics_forward': (C.c_int, [C.POINTER(ValMetricsDesc), _i, _i, _p]),
     'dir_mano_forward_pair': (C.c_int, [C.POINTER(ManoTables), _p, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _i, _p]),
     'dir_mano_backward_pair': (C.c_int, [C.POINTER(ManoTables), _p, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _i, _p, _i, _p, _i, _i, _i, _p]),
     'dir_regress_backward': (C.c_int, [_p] * 17 + [_i, _p]),

@@ -205,15 +205,19 @@ class TrainBatches(object):
     dense are not read from files: they are rendered per batch (csrc/render.hip, render_data's rules) from the camera-frame vertices of
     gt_batch, whose tuple augment_batch then reuses, so the ground-truth MANO runs once; only img/ is decoded.  These frames are the
     arrays cv.imwrite would receive, without the JPEG round trip the files have been through, so they are not the file path's bytes.
-    The faces are the right GT layer's (ManoLayer.get_faces()); a layer without faces (a checkpoint without th_faces) is an error."""
+    The faces are the right GT layer's (ManoLayer.get_faces()); a layer without faces (a checkpoint without th_faces) is an error.
+
+    shuffle=False: every pass reads the split in file order (the reference's test loader, train.py:215-220; drop_last as well) and draws
+    no permutation.  `self.last_perm` holds the file indices of the pass that was started last, in the order they are read."""
 
     def __init__(self, data_path, mano_layer, split='train', batch_size=32, workers=8, seed=0, augment=True, records=True, device='cuda',
-                 dense_color=None):
+                 dense_color=None, shuffle=True):
         from .dataset import InterHandSplit
         self.data_path, self.split, self.mano_layer = data_path, split, mano_layer
         self.bs, self.workers, self.augment, self.records = batch_size, workers, augment, records
         self.device = torch.device(device)
         self.rng = np.random.default_rng(seed)
+        self.seed, self.shuffle, self.last_perm = seed, bool(shuffle), None
         self.n = len(InterHandSplit(data_path, split))
         self.epoch = 0
         self.last_params, self.last_seed = None, None
@@ -229,7 +233,8 @@ class TrainBatches(object):
 
     def __iter__(self):
         from .dataset import IMG_SIZE as S, DecodeRing
-        perm = self.rng.permutation(self.n)[:len(self) * self.bs]
+        perm = (self.rng.permutation(self.n) if self.shuffle else np.arange(self.n))[:len(self) * self.bs]
+        self.last_perm = perm
         self.epoch += 1
         if len(perm) == 0:
             return

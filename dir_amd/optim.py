@@ -4,6 +4,7 @@
                                        (betas (0.9, 0.999), eps 1e-8, weight_decay 0.01), same `state_dict()` layout, so a
                                        reference checkpoint's 'optimizer' entry loads and a saved one resumes under torch
   CosineAnnealingLR    train.py:229-230 optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max, eta_min=0) (closed form)
+  MultiStepLR          train.py:231-232 optim.lr_scheduler.MultiStepLR(optimizer, [30], gamma=0.1) (torch's chained form)
   save_checkpoint / load_checkpoint    train.py:127-149  {'net', 'optimizer', 'schedule', 'last_epoch'}
 The parameters are moved into ONE contiguous fp32 buffer (each tensor becomes a view of it), gradients into a second one
 (`.grad` of each parameter is a view), the two Adam moments are flat as well: `step()` is a single dir_adamw_step launch over
@@ -161,6 +162,44 @@ class CosineAnnealingLR(object):
         self.T_max, self.eta_min = sd['T_max'], sd['eta_min']
         self.base_lrs, self.last_epoch = list(sd['base_lrs']), sd['last_epoch']
         for g, lr in zip(self.optimizer.param_groups, sd.get('_last_lr', self.get_lr())):
+            g['lr'] = lr
+
+
+class MultiStepLR(object):
+    """optim.lr_scheduler.MultiStepLR(optimizer, milestones, gamma) as train.py:231-232,84 uses it: step() once per epoch; when the epoch
+    count reaches a milestone the current lr is multiplied by gamma (once per time the milestone is listed) -- torch's chained form, so the
+    values are torch's to the bit.  state_dict() has torch's layout (milestones as a Counter)."""
+
+    def __init__(self, optimizer, milestones, gamma=0.1, last_epoch=-1):
+        from collections import Counter
+        self.optimizer, self.milestones, self.gamma = optimizer, Counter(milestones), gamma
+        self.base_lrs = [g.get('initial_lr', g['lr']) for g in optimizer.param_groups]
+        for g, b in zip(optimizer.param_groups, self.base_lrs):
+            g.setdefault('initial_lr', b)
+        self.last_epoch = last_epoch
+        self.step()
+
+    def get_lr(self):
+        n = self.milestones.get(self.last_epoch, 0)
+        return [g['lr'] * self.gamma ** n if n else g['lr'] for g in self.optimizer.param_groups]
+
+    def get_last_lr(self):
+        return [g['lr'] for g in self.optimizer.param_groups]
+
+    def step(self):
+        self.last_epoch += 1
+        for g, lr in zip(self.optimizer.param_groups, self.get_lr()):
+            g['lr'] = lr
+
+    def state_dict(self):
+        return {'milestones': self.milestones, 'gamma': self.gamma, 'base_lrs': list(self.base_lrs), 'last_epoch': self.last_epoch,
+                '_step_count': self.last_epoch + 1, '_last_lr': self.get_last_lr()}
+
+    def load_state_dict(self, sd):
+        from collections import Counter
+        self.milestones, self.gamma = Counter(sd['milestones']), sd['gamma']
+        self.base_lrs, self.last_epoch = list(sd['base_lrs']), sd['last_epoch']
+        for g, lr in zip(self.optimizer.param_groups, sd['_last_lr']):
             g['lr'] = lr
 
 

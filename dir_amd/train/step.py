@@ -60,12 +60,14 @@ def token_stage_train_step(named_params, prefix, mano_tables_lr, feat_nhwc, prev
 def train_step(named_params, buffers, img, target, meta_info, faces, optimizer, overlap_allreduce=True):
     """One optimisation step of the whole network (train.py:64-70: zero_grad, forward, sum(loss).backward(), optimizer.step):
     named_params {DIR state-dict key -> nn.Parameter registered with `optimizer` (FlatAdamW)}, buffers {key -> tensor} (BatchNorm running
-    statistics -- updated in place --, MANO tables).  Returns the 42 loss terms.  overlap_allreduce: bucketed gradient exchange issued
+    statistics -- updated in place --, MANO tables).  Returns the 42 loss terms; the step's own stage dicts (net.forward's `outs`, training
+    mode) stay reachable as `optimizer.last_outs` until the next call (what a training driver draws from).  overlap_allreduce: bucketed gradient exchange issued
     during the backward pass (default) or one exchange after it (the round-2 path; same result, bit-identical for two ranks)."""
     from . import net as TN
     P = {k: v.data for k, v in named_params.items()}
     P.update(buffers)
     outs, ctx = TN.forward(P, img, scale_owner=optimizer)
+    optimizer.last_outs = outs
     loss = TN.losses(outs, target, meta_info, faces)
     optimizer.zero_grad()
     if not overlap_allreduce:
@@ -102,12 +104,14 @@ class GraphedTrainStep(object):
     the operand scales are calibrated (`warm` eager steps), then replayed; FlatAdamW.step (whose learning rate and step count are launch
     ARGUMENTS: train.py:127-149 changes them every step) and the gradient exchange of N > 1 ranks run after the replay.  The operand scales are
     arguments too, so every DIR_TRAIN_RECALIBRATE steps one step runs eagerly (re-measuring them) and the graph is captured again.
-    Inputs are copied into fixed buffers; the returned loss tensors are the graph's own (valid until the next call).  Same kernels, same order:
+    Inputs are copied into fixed buffers; the returned loss tensors are the graph's own (valid until the next call), and so are the stage
+    dicts of the last step, kept as `self.outs` (net.forward's `outs`).  Same kernels, same order:
     the parameters after n steps equal train_step's bit for bit (tests/test_gpu_full_bwd.py)."""
 
     def __init__(self, named_params, buffers, optimizer, faces, warm=2):
         self.named_params, self.buffers, self.optimizer, self.faces, self.warm = named_params, buffers, optimizer, faces, int(warm)
         self.graph, self.static, self.loss, self.calls, self.since_capture = None, None, None, 0, 0
+        self.outs, self._graph_outs = None, None
 
     def _stage(self, img, target, meta_info):
         if self.static is None:
@@ -128,6 +132,7 @@ class GraphedTrainStep(object):
         P = {k: v.data for k, v in self.named_params.items()}
         P.update(self.buffers)
         outs, ctx = TN.forward(P, img, scale_owner=opt)
+        self.outs = outs
         loss = TN.losses(outs, target, meta, self.faces)
         opt.zero_grad()
         G = TN.backward(P, ctx, outs, target, meta, self.faces)
@@ -156,8 +161,9 @@ class GraphedTrainStep(object):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 self.loss = self._body()
-            self.graph, self.since_capture = g, 0
+            self.graph, self.since_capture, self._graph_outs = g, 0, self.outs
         self.graph.replay()
+        self.outs = self._graph_outs
         self.since_capture += 1
         D.average_gradients(self.optimizer.flat_grad)
         self.optimizer.step()

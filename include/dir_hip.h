@@ -29,7 +29,7 @@ extern "C" {
 #define DIR_E_LAUNCH (-2)   /* hipLaunchKernel / HIP runtime error          */
 #define DIR_E_NODEVICE (-3) /* no gfx950 device visible                     */
 
-#define DIR_ABI_VERSION 41
+#define DIR_ABI_VERSION 42
 
 int dir_abi_version(void);
 const char* dir_last_error(void);
@@ -777,6 +777,29 @@ typedef struct dir_eval_outputs {
 } dir_eval_outputs;
 int dir_eval_metrics_forward(const dir_eval_inputs* in_host, const dir_eval_outputs* out_host, int B, int root_joint,
                              int use_scale, void* stream);
+
+/* f1d: the validation metric of the training loop, InterHandDataset.evaluate (dataset/interhand.py:262-315) for every stage of a
+ * batch, accumulated as Trainer.test_model does (train.py:157-181).  Root = MANO joint 9 of pd_joint_xyz_* / joint_3d_* (no joint
+ * regression, whatever the model's root_joint), scale = |J9 - J0|_gt / |J9 - J0|_pred per hand and sample, errors = L2 norms of
+ * (pred - root_pred) * scale - (gt - root_gt) in fp32.  Hand index 0 = left, 1 = right; all inputs device fp32, contiguous:
+ * joints_pd[s][h] [B,21,3] / verts_pd[s][h] [B,778,3] = outs_list[s]['pd_joint_xyz_*' / 'pd_mesh_xyz_*'] for s < n_stages (1..8),
+ * joints_gt[h] / verts_gt[h] = targets['joint_3d_*' / 'mesh_3d_*'].
+ * sample_sums: double [n_stages][B][4] scratch the caller owns; on return (of the stream) it holds every sample's sums of norms
+ * (joint L, joint R, vert L, vert R; metres).  acc: double [n_stages][4], batches: long long [1]: the caller's running sums; each
+ * call ADDS the batch means in millimetres (sum / (B * 21 | 778) * 1000) to acc and 1 to *batches, in a fixed order (no atomics: the
+ * same calls give the same bits).  MPJPE_s left = acc[s][0] / *batches, and so on.  A predicted bone of length 0 gives inf / NaN as in
+ * the reference.  B = 0 is a no-op.  Two launches, no host synchronisation, nothing allocated. */
+#define DIR_VAL_MAX_STAGES 8
+typedef struct dir_val_metrics_desc {
+    const float* joints_pd[DIR_VAL_MAX_STAGES][2];
+    const float* verts_pd[DIR_VAL_MAX_STAGES][2];
+    const float* joints_gt[2];
+    const float* verts_gt[2];
+    double* sample_sums;
+    double* acc;
+    long long* batches;
+} dir_val_metrics_desc;
+int dir_val_metrics_forward(const dir_val_metrics_desc* desc_host, int n_stages, int B, void* stream);
 
 /* f1c: the ground-truth MANO layer, models/manolayer.py:251-323 (ManoLayer.forward; rodrigues_batch :32-48), the
  * formulation dataset/interhand.py:130-149 uses to synthesise GT.  Tables in the dir_mano_tables packing (comps = the full
