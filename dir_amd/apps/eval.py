@@ -5,6 +5,8 @@
                                        per-sample errors stay on the GPU until summarize()/save_txt(), which reduce and
                                        format exactly like :246-306 (numpy float32 means, *1000 for mm, '%.3f' files)
   evaluate        apps/eval.py:137-241 the loop: network(...) -> metrics.update(...)
+  --penetration   (not in the reference: apps/eval.py:134 sets up inter_volume_list and never fills it) inter-hand penetration depth and
+                                       intersection volume of the predictions, utils/penetration.py; off by default
   evaluate_from_disk / main   apps/eval.py:88-136  the command line (`python -m dir_amd.apps.eval --model DIR.pth --data_path ... --bs 256
                                        --root_joint 0`): checkpoint -> DIR, the prepared split from disk through dir_amd.apps.dataset
                                        (decode ring -> uint8 frames -> two forwards in flight), GT on the GPU, the same report / files
@@ -181,10 +183,12 @@ _SKIP_DEVICE_DECODE = __import__('os').environ.get('DIR_EVAL_SKIP_DEVICE_DECODE'
 
 
 def evaluate_from_disk(eng, data_path, J_regressor, mano_layer, bs=256, root_joint=0, scale=True, split='test', workers=8,
-                       stage_num=3, indices=None, progress=None, source='jpeg', nslot=3):
+                       stage_num=3, indices=None, progress=None, source='jpeg', nslot=3, penetration=None, penetration_gt=False):
     """apps/eval.py:121-241 from the prepared split on disk, at pipeline speed: decode processes (dataset.DecodeRing) -> pinned uint8
     batches -> two forwards in flight (engine.ForwardPipeline over uint8 input slots; the normalisation runs inside the stem kernel,
     proj_feat is not produced: the evaluation never reads it) -> GT MANO + metrics on the GPU.  `eng`: a DirEngine.
+    penetration: a utils.penetration.PenetrationMetrics that scores every batch as well (penetration_gt: the ground-truth meshes too, on the
+    loop's stream beside the other metrics), on the slot's own stream: ordered after the forward it reads and before the slot's next one by stream order, with no host wait added.
     Returns (EvalMetrics, {'images', 'seconds', 'images_per_sec'})."""
     import time
     from ..engine import ForwardPipeline
@@ -216,6 +220,11 @@ def evaluate_from_disk(eng, data_path, J_regressor, mano_layer, bs=256, root_joi
         res = [{k: (v[:n] if torch.is_tensor(v) else v) for k, v in o.items()} for o in outs[:3]]
         gt = gt_batch(mano_layer, annos[:n])
         m.update(res, (None,) * 2 + gt)          # data[0] image / data[1] mask are not read by the metric maths (apps/eval.py:151-241)
+        if penetration is not None:
+            with torch.cuda.stream(pipe.streams[slot]):
+                penetration.update(res)
+            if penetration_gt:
+                penetration.update_gt((None,) * 2 + gt)      # on the loop's stream, where gt was made and lives: no cross-stream edge
         pending[slot] = None
 
     t0, seen = time.perf_counter(), 0
@@ -284,6 +293,12 @@ def main(argv=None):
                     "uint8 shards of dir_amd.apps.dataset.write_u8_shards (no decode in the loop)")
     ap.add_argument('--workers', type=int, default=16, help='decode processes (jpeg) / copy threads (u8); more than the CPUs the process may use is slower')
     ap.add_argument('--result_dir', type=str, default='./result/DIR-PoseEmb-Wrist')
+    ap.add_argument('--penetration', action='store_true', help='also measure how far the two predicted hands pass through each other (penetration depth, '
+                    'penetrating vertices, intersection volume: dir_amd.utils.penetration); prints a block after the report and writes penetration.txt')
+    ap.add_argument('--volume_pitch', type=float, default=0.005, help='with --penetration: the lattice pitch of the intersection volume in metres; 0 = no volume')
+    ap.add_argument('--seal_wrist', choices=['auto', 'on', 'off'], default='auto', help="with --penetration: close each hand's open wrist with a fan of "
+                    "triangles first; auto = when the face table has that single boundary loop (real MANO has, a synthetic table has not)")
+    ap.add_argument('--penetration_gt', action='store_true', help='with --penetration: the same measures for the ground-truth meshes (penetration_gt.txt)')
     opt = ap.parse_args(argv)
     state = torch.load(opt.model, map_location='cpu', weights_only=False)
     state = state['net'] if isinstance(state, dict) and 'net' in state else state
@@ -292,10 +307,26 @@ def main(argv=None):
     eng = DirEngine(state, dtype={'f16': torch.float16, 'bf16': torch.bfloat16, 'f32': torch.float32}[opt.dtype], root_joint=0, arith=opt.arith)     # apps/eval.py:104: DIR(21, './misc/mano')
     mano_layer = gt_layers_from_checkpoint(state)
     J_regressor = {s: Jr(mano_layer[s].J_regressor) for s in ('left', 'right')}
+    pen = None
+    if opt.penetration:
+        from ..utils import penetration as PN
+        from ..utils.vis_utils import faces_from_layers
+        fl, fr, sealed = PN.hand_faces(faces_from_layers(mano_layer), seal=opt.seal_wrist, device=eng.device)
+        pen = PN.PenetrationMetrics((fl, fr), stage_num=3, volume_pitch=opt.volume_pitch)
+        pen.sealed = sealed
+    elif opt.penetration_gt:
+        ap.error('--penetration_gt needs --penetration')
     m, rate = evaluate_from_disk(eng, opt.data_path, J_regressor, mano_layer, bs=opt.bs, root_joint=opt.root_joint, scale=opt.scale,
-                                 workers=opt.workers, source=opt.source)
+                                 workers=opt.workers, source=opt.source, penetration=pen, penetration_gt=opt.penetration_gt)
     m.save_txt(opt.result_dir)
     print(m.report())
+    if pen is not None:
+        m.penetration = pen
+        pen.save_txt(opt.result_dir)
+        print(pen.report())
+        if opt.penetration_gt:
+            print(pen.report(gt=True))
+        print('    wrists %s (--seal_wrist %s)' % ('sealed with a fan of triangles' if sealed else 'left open', opt.seal_wrist))
     print('%d images in %.1f s: %.0f images/s from files' % (rate['images'], rate['seconds'], rate['images_per_sec']))
     return m
 

@@ -106,17 +106,27 @@ def report_lines(res, n_stages):
     return printed, logged
 
 
-def validate(model, batches, logger=None, dtype=None, quiet=False):
+def validate(model, batches, logger=None, dtype=None, quiet=False, penetration=False):
     """Trainer.test_model (train.py:156-202).  model: a dir_amd.models.dir.DIR on the GPU; batches: an iterable of (inputs, targets,
     meta_info) -- TrainBatches(data_path, gt_layers, split, batch_size, augment=False, shuffle=False); one with `seed` and `rng` is re-seeded
     first, so that every validation sees the same noise.  dtype: the feature-map type of the eval-mode engine (torch.float16 |
     bfloat16 | float32; None = model.compute_dtype as it is).  The packed engine is dropped first (model.refresh()): training writes BatchNorm
-    running statistics through raw pointers, which no version counter sees."""
+    running statistics through raw pointers, which no version counter sees.
+    penetration: also measure how far the last stage's two hands pass through each other (utils/penetration.py, wrists as the face table
+    has them, no volume): adds 'penetration_depth_mm' (mean over the samples) and 'penetration_rate' (share of samples with a penetrating
+    vertex) to the result and one line to the report; 'error', which selects best.pth, is not touched."""
     _capi.require_cuda(*list(model.parameters()))
     if dtype is not None:
         model.compute_dtype = dtype
     n_stages = _n_stages(model)
     metrics = ValMetrics(n_stages)
+    pen = None
+    if penetration:
+        from ..utils import penetration as PN
+        from ..utils.vis_utils import two_hand_faces
+        dev = next(model.parameters()).device
+        pen = PN.PenetrationMetrics(PN.hand_faces(two_hand_faces(model.init_regressor.mano_layer_right.th_faces.cpu().numpy()), device=dev)[:2],
+                                    stage_num=n_stages, volume_pitch=None)
     if hasattr(batches, 'rng') and hasattr(batches, 'seed'):
         batches.rng = np.random.default_rng(batches.seed)
     model.eval()
@@ -126,10 +136,18 @@ def validate(model, batches, logger=None, dtype=None, quiet=False):
             for inputs, targets, meta_info in batches:
                 outs_list, _ = model(inputs, targets, meta_info)
                 metrics.update(outs_list, targets)
+                if pen is not None:
+                    pen.update(outs_list)
     finally:
         model.train()                                     # train.py:201
     res = metrics.result()
     printed, logged = report_lines(res, n_stages)
+    if pen is not None and pen.batches:
+        ps = pen.summarize()
+        res['penetration_depth_mm'], res['penetration_rate'] = ps['depth_mean_mm'], ps['rate']
+        line = 'penetration_{}: depth {} mm, rate {}'.format(n_stages - 1, ps['depth_mean_mm'], ps['rate'])
+        printed.append(line)
+        logged.append(line)
     if not quiet:
         print('\n'.join(printed))
     if logger is not None:
@@ -248,7 +266,7 @@ def _count_batches(model, steps):
 
 def fit(model, batches, val_batches=None, output_root='./output', optimizer=None, schedule=None, total_epoch=50, lr=5e-4,
         lr_scheduler='cosine', step='graphed', print_iter=100, draw_iter=100, eval_interval=1, eval_dtype=None, seed=0, max_steps=None,
-        continue_train=None, name='DIR', logger=None, on_step=None):
+        continue_train=None, name='DIR', logger=None, on_step=None, eval_penetration=False):
     """train() of train.py:58-91.  model: a DIR on the GPU, in training mode from here on; batches: TrainBatches of the train split (its
     `rng` is re-seeded per epoch from (seed, epoch)); val_batches: what validate() takes, or None = no validation, no best.pth.
     step: 'graphed' (GraphedTrainStep) | 'eager' (train_step) | 'module' (model(...); sum(loss).backward(); optimizer.step()).
@@ -327,7 +345,7 @@ def fit(model, batches, val_batches=None, output_root='./output', optimizer=None
             logger.info('Save checkpoint to {}'.format(os.path.join(ckpt_dir, 'latest.pth')))
             state['epochs'] += 1
             if val_batches is not None and not epoch % eval_interval:
-                res = validate(model, val_batches, logger=logger, dtype=eval_dtype)
+                res = validate(model, val_batches, logger=logger, dtype=eval_dtype, penetration=eval_penetration)
                 state['last_val'] = res
                 if res['error'] < state['min_error']:
                     save_checkpoint(os.path.join(ckpt_dir, 'best.pth'), model, optimizer, schedule, epoch)
@@ -385,6 +403,8 @@ def build_parser():
     ap.add_argument('--max_steps', type=int, default=None, help='stop early (tests, smoke runs)')
     ap.add_argument('--backbone', choices=['resnet50', 'hrnet_w48'], default='resnet50')
     ap.add_argument('--extra_stages', type=int, default=0)
+    ap.add_argument('--eval_penetration', action='store_true', help="add the last stage's mean inter-hand penetration depth and penetration rate to "
+                    'the validation lines (best.pth is still chosen by the joint error)')
     return ap
 
 
@@ -410,7 +430,7 @@ def main(argv=None):
                            augment=False, shuffle=False, dense_color=opt.dense_color)
     return fit(model, batches, val, output_root=opt.output_root, total_epoch=opt.total_epoch, lr=opt.lr, lr_scheduler=opt.lr_scheduler,
                step=opt.step, print_iter=opt.print_iter, draw_iter=opt.draw_iter, eval_interval=max(1, opt.eval_interval), seed=opt.seed,
-               max_steps=opt.max_steps, continue_train=opt.continue_train, name=opt.experiment_name)
+               max_steps=opt.max_steps, continue_train=opt.continue_train, name=opt.experiment_name, eval_penetration=opt.eval_penetration)
 
 
 if __name__ == '__main__':

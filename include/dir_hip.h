@@ -29,7 +29,7 @@ extern "C" {
 #define DIR_E_LAUNCH (-2)   /* hipLaunchKernel / HIP runtime error          */
 #define DIR_E_NODEVICE (-3) /* no gfx950 device visible                     */
 
-#define DIR_ABI_VERSION 42
+#define DIR_ABI_VERSION 43
 
 int dir_abi_version(void);
 const char* dir_last_error(void);
@@ -1102,6 +1102,36 @@ int dir_render_shaded(const float* verts, const int32_t* faces, const void* adja
  * project's own coverage rule and palette (csrc/render.hip) -- it is NOT OpenCV's drawing. */
 int dir_render_joints(uint8_t* image, const float* uv_left, const float* uv_right, int B, int S, float joint_radius, float bone_radius,
                       void* stream);
+
+/* ---- inter-hand penetration: how far two meshes pass through each other (csrc/penetration.hip) ----
+ * The measures are ObMan's (Hasson et al. 2019); the rules (generalised winding number with |w| > 0.5 as the inside test, closest point
+ * on the closed triangle, which faces are skipped, the voxel lattice) are written out in the header comment of csrc/penetration.hip.
+ * Generic in the mesh sizes.  Device pointers:
+ *   verts_a  float32 [B,Va,3], faces_a int32 [Fa,3]; verts_b float32 [B,Vb,3], faces_b int32 [Fb,3]: two batched meshes in ONE frame,
+ *            each with one face table for the whole batch.  A face with a repeated index or an index outside 0..V-1 is skipped.
+ * dir_mesh_penetration queries A's vertices against mesh B (direction 0) and B's against A (direction 1):
+ *   winding, dist  float32 [B,Va+Vb] or NULL: per vertex, A's vertices first, the winding number with respect to the OTHER mesh and the
+ *                  distance to its surface (metres; +inf when every face is skipped)
+ *   count          int32 [B,2]    vertices inside the other mesh, per direction
+ *   max_depth      float32 [B,2]  the largest distance over those vertices, 0 when there are none
+ *   sum_depth      float32 [B,2]  the sum of the distances over those vertices
+ * The results are the same bits from run to run and for a sample in any batch.
+ * dir_mesh_intersection_volume counts the points of the lattice (i h, j h, k h) inside both meshes, over the intersection of the two
+ * bounding boxes; everything is decided on the device:
+ *   cells    int32 [B]    lattice points in the boxes' intersection (0: the boxes are disjoint); max_cells + 1 when there are more than
+ *                         max_cells, or when a lattice index exceeds 2^24 -- then nothing is examined
+ *   n_both   int32 [B]    lattice points inside both meshes (0 when nothing was examined)
+ *   volume   float32 [B]  n_both * h^3 (cubic metres), NaN when nothing was examined because of max_cells
+ * Sizes outside the limits below, B <= 0, h <= 0 or a null pointer give DIR_E_INVALID before any launch. */
+#define DIR_MESH_MAX_VERTS 4096
+#define DIR_MESH_MAX_FACES 8192
+#define DIR_MESH_MAX_BATCH 65536
+#define DIR_MESH_MAX_CELLS (1 << 24)
+int dir_mesh_penetration(const float* verts_a, const int32_t* faces_a, const float* verts_b, const int32_t* faces_b, int B, int Va, int Fa,
+                         int Vb, int Fb, float* winding, float* dist, int32_t* count, float* max_depth, float* sum_depth, void* stream);
+int dir_mesh_intersection_volume(const float* verts_a, const int32_t* faces_a, const float* verts_b, const int32_t* faces_b, int B, int Va,
+                                 int Fa, int Vb, int Fb, float h, int max_cells, float* volume, int32_t* n_both, int32_t* cells,
+                                 void* stream);
 
 #ifdef __cplusplus
 }
