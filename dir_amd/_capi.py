@@ -133,7 +133,7 @@ class RenderLights(C.Structure):         # dir_render_lights
                 ('shininess', C.c_float)]
 
 
-ABI_VERSION = 43         # DIR_ABI_VERSION (include/dir_hip.h)
+ABI_VERSION = 44         # DIR_ABI_VERSION (include/dir_hip.h)
 DT_F32, DT_BF16, DT_F16X3, DT_F16X1, DT_F16X3P, DT_F16X1P, DT_F16 = 0, 1, 3, 4, 5, 6, 7      # DT_F16: f16 STORAGE (round 5)
 CONV_RELU, CONV_PRE_RELU = 1, 2
 
@@ -275,6 +275,9 @@ _SIGNATURES = {
     'dir_render_shaded': (C.c_int, [_p, _p, _p, _p, _p, _p, _p, C.POINTER(RenderLights), _p, _i, _i, _p, C.c_longlong, _p, _p, _p, _p, _p, _p]),
     'dir_mesh_penetration': (C.c_int, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     'dir_mesh_intersection_volume': (C.c_int, [_p, _p, _p, _p, _i, _i, _i, _i, _i, C.c_float, _i, _p, _p, _p, _p]),
+    'dir_procrustes_align': (C.c_int, [_p, _p, _i, _i, _i, _p, _p, _p, _p]),
+    'dir_point_set_nn': (C.c_int, [_p, _p, _i, _i, _i, _p, _p, _p]),
+    'dir_threshold_counts': (C.c_int, [_p, C.c_longlong, _p, _i, _p, _p]),
 }
 
 

@@ -7,6 +7,8 @@
   evaluate        apps/eval.py:137-241 the loop: network(...) -> metrics.update(...)
   --penetration   (not in the reference: apps/eval.py:134 sets up inter_volume_list and never fills it) inter-hand penetration depth and
                                        intersection volume of the predictions, utils/penetration.py; off by default
+  --aligned       (not in the reference) PA-MPJPE / PA-MPVPE, PCK curves with their AUC and mesh F-scores at 5 / 15 mm after a per-hand
+                                       similarity alignment, utils/alignment.py; off by default
   evaluate_from_disk / main   apps/eval.py:88-136  the command line (`python -m dir_amd.apps.eval --model DIR.pth --data_path ... --bs 256
                                        --root_joint 0`): checkpoint -> DIR, the prepared split from disk through dir_amd.apps.dataset
                                        (decode ring -> uint8 frames -> two forwards in flight), GT on the GPU, the same report / files
@@ -183,12 +185,14 @@ _SKIP_DEVICE_DECODE = __import__('os').environ.get('DIR_EVAL_SKIP_DEVICE_DECODE'
 
 
 def evaluate_from_disk(eng, data_path, J_regressor, mano_layer, bs=256, root_joint=0, scale=True, split='test', workers=8,
-                       stage_num=3, indices=None, progress=None, source='jpeg', nslot=3, penetration=None, penetration_gt=False):
+                       stage_num=3, indices=None, progress=None, source='jpeg', nslot=3, penetration=None, penetration_gt=False, aligned=None):
     """apps/eval.py:121-241 from the prepared split on disk, at pipeline speed: decode processes (dataset.DecodeRing) -> pinned uint8
     batches -> two forwards in flight (engine.ForwardPipeline over uint8 input slots; the normalisation runs inside the stem kernel,
     proj_feat is not produced: the evaluation never reads it) -> GT MANO + metrics on the GPU.  `eng`: a DirEngine.
     penetration: a utils.penetration.PenetrationMetrics that scores every batch as well (penetration_gt: the ground-truth meshes too, on the
     loop's stream beside the other metrics), on the slot's own stream: ordered after the forward it reads and before the slot's next one by stream order, with no host wait added.
+    aligned: a utils.alignment.AlignedMetrics that scores every batch as well, on the slot's own stream too.  It reads the ground truth and the
+    batch's joint errors, which the loop's stream makes: the slot's stream waits for them on the device (an event), never the host.
     Returns (EvalMetrics, {'images', 'seconds', 'images_per_sec'})."""
     import time
     from ..engine import ForwardPipeline
@@ -219,7 +223,15 @@ def evaluate_from_disk(eng, data_path, J_regressor, mano_layer, bs=256, root_joi
         outs = pipe.wait(slot)
         res = [{k: (v[:n] if torch.is_tensor(v) else v) for k, v in o.items()} for o in outs[:3]]
         gt = gt_batch(mano_layer, annos[:n])
-        m.update(res, (None,) * 2 + gt)          # data[0] image / data[1] mask are not read by the metric maths (apps/eval.py:151-241)
+        out = m.update(res, (None,) * 2 + gt)    # data[0] image / data[1] mask are not read by the metric maths (apps/eval.py:151-241)
+        if aligned is not None:
+            made = torch.cuda.Event()
+            made.record()                            # gt and the batch's joint errors are queued on the loop's stream
+            pipe.streams[slot].wait_event(made)
+            for t in (gt[1], gt[3], out['joint_err']):
+                t.record_stream(pipe.streams[slot])  # made on the loop's stream, read on the slot's: the allocator must not hand them out early
+            with torch.cuda.stream(pipe.streams[slot]):
+                aligned.update(res, (None,) * 2 + gt, eval_out=out)
         if penetration is not None:
             with torch.cuda.stream(pipe.streams[slot]):
                 penetration.update(res)
@@ -299,6 +311,9 @@ def main(argv=None):
     ap.add_argument('--seal_wrist', choices=['auto', 'on', 'off'], default='auto', help="with --penetration: close each hand's open wrist with a fan of "
                     "triangles first; auto = when the face table has that single boundary loop (real MANO has, a synthetic table has not)")
     ap.add_argument('--penetration_gt', action='store_true', help='with --penetration: the same measures for the ground-truth meshes (penetration_gt.txt)')
+    ap.add_argument('--aligned', action='store_true', help='also report PA-MPJPE / PA-MPVPE (per-hand similarity alignment, proper rotations only), the AUC '
+                    'of the PCK curves over 0-50 mm and mesh F-scores at 5 / 15 mm (dir_amd.utils.alignment); prints a block after the report and writes '
+                    'pa_joint_*_error.txt, pa_mesh_*_error.txt, fscore.txt and pck.txt')
     opt = ap.parse_args(argv)
     state = torch.load(opt.model, map_location='cpu', weights_only=False)
     state = state['net'] if isinstance(state, dict) and 'net' in state else state
@@ -316,8 +331,12 @@ def main(argv=None):
         pen.sealed = sealed
     elif opt.penetration_gt:
         ap.error('--penetration_gt needs --penetration')
+    aligned = None
+    if opt.aligned:
+        from ..utils.alignment import AlignedMetrics
+        aligned = AlignedMetrics(J_regressor, stage_num=3, root_joint=opt.root_joint, scale=opt.scale)
     m, rate = evaluate_from_disk(eng, opt.data_path, J_regressor, mano_layer, bs=opt.bs, root_joint=opt.root_joint, scale=opt.scale,
-                                 workers=opt.workers, source=opt.source, penetration=pen, penetration_gt=opt.penetration_gt)
+                                 workers=opt.workers, source=opt.source, penetration=pen, penetration_gt=opt.penetration_gt, aligned=aligned)
     m.save_txt(opt.result_dir)
     print(m.report())
     if pen is not None:
@@ -327,6 +346,10 @@ def main(argv=None):
         if opt.penetration_gt:
             print(pen.report(gt=True))
         print('    wrists %s (--seal_wrist %s)' % ('sealed with a fan of triangles' if sealed else 'left open', opt.seal_wrist))
+    if aligned is not None:
+        m.aligned = aligned                  # as m.penetration above: main's caller gets the accumulator with the metrics
+        aligned.save_txt(opt.result_dir)
+        print(aligned.report())
     print('%d images in %.1f s: %.0f images/s from files' % (rate['images'], rate['seconds'], rate['images_per_sec']))
     return m
 

@@ -106,7 +106,7 @@ def report_lines(res, n_stages):
     return printed, logged
 
 
-def validate(model, batches, logger=None, dtype=None, quiet=False, penetration=False):
+def validate(model, batches, logger=None, dtype=None, quiet=False, penetration=False, aligned=False):
     """Trainer.test_model (train.py:156-202).  model: a dir_amd.models.dir.DIR on the GPU; batches: an iterable of (inputs, targets,
     meta_info) -- TrainBatches(data_path, gt_layers, split, batch_size, augment=False, shuffle=False); one with `seed` and `rng` is re-seeded
     first, so that every validation sees the same noise.  dtype: the feature-map type of the eval-mode engine (torch.float16 |
@@ -114,7 +114,11 @@ def validate(model, batches, logger=None, dtype=None, quiet=False, penetration=F
     running statistics through raw pointers, which no version counter sees.
     penetration: also measure how far the last stage's two hands pass through each other (utils/penetration.py, wrists as the face table
     has them, no volume): adds 'penetration_depth_mm' (mean over the samples) and 'penetration_rate' (share of samples with a penetrating
-    vertex) to the result and one line to the report; 'error', which selects best.pth, is not touched."""
+    vertex) to the result and one line to the report; 'error', which selects best.pth, is not touched.
+    aligned: also the last stage's errors after a per-hand similarity alignment (utils/alignment.py: joints on joints, vertices on vertices,
+    with scale, proper rotations only), from the same 'pd_joint_xyz_*' / 'pd_mesh_xyz_*' and targets ValMetrics reads: adds 'PA_MPJPE_<last>' and
+    'PA_MPVPE_<last>' as {'left', 'right', 'all'} (mm; a hand whose joint or mesh alignment does not exist is left out of both, as AlignedMetrics
+    does) and one line to the report; 'error' is not touched."""
     _capi.require_cuda(*list(model.parameters()))
     if dtype is not None:
         model.compute_dtype = dtype
@@ -127,6 +131,9 @@ def validate(model, batches, logger=None, dtype=None, quiet=False, penetration=F
         dev = next(model.parameters()).device
         pen = PN.PenetrationMetrics(PN.hand_faces(two_hand_faces(model.init_regressor.mano_layer_right.th_faces.cpu().numpy()), device=dev)[:2],
                                     stage_num=n_stages, volume_pitch=None)
+    pa_sums, pa_points = [], None
+    if aligned:
+        from ..utils.alignment import procrustes_align
     if hasattr(batches, 'rng') and hasattr(batches, 'seed'):
         batches.rng = np.random.default_rng(batches.seed)
     model.eval()
@@ -138,6 +145,12 @@ def validate(model, batches, logger=None, dtype=None, quiet=False, penetration=F
                 metrics.update(outs_list, targets)
                 if pen is not None:
                     pen.update(outs_list)
+                if aligned:
+                    last = outs_list[n_stages - 1]
+                    # per-sample sums in float64 (NaN: no alignment exists), read once after the loop
+                    pa_sums.append(torch.stack([procrustes_align(last[k + side], targets[g + side])['err'].double().sum(1)
+                                                for k, g in (('pd_joint_xyz_', 'joint_3d_'), ('pd_mesh_xyz_', 'mesh_3d_')) for side in SIDES], 1))
+                    pa_points = [last[k + side].shape[1] for k in ('pd_joint_xyz_', 'pd_mesh_xyz_') for side in SIDES]
     finally:
         model.train()                                     # train.py:201
     res = metrics.result()
@@ -146,6 +159,19 @@ def validate(model, batches, logger=None, dtype=None, quiet=False, penetration=F
         ps = pen.summarize()
         res['penetration_depth_mm'], res['penetration_rate'] = ps['depth_mean_mm'], ps['rate']
         line = 'penetration_{}: depth {} mm, rate {}'.format(n_stages - 1, ps['depth_mean_mm'], ps['rate'])
+        printed.append(line)
+        logged.append(line)
+    if pa_sums:
+        sums = torch.cat(pa_sums, 0).cpu().numpy()                          # [n, (joint left, joint right, mesh left, mesh right)]
+        for h in range(2):                                                  # a hand without a joint OR a mesh alignment is left out of both
+            none = np.isnan(sums[:, h]) | np.isnan(sums[:, 2 + h])
+            sums[none, h], sums[none, 2 + h] = np.nan, np.nan
+        mean = np.array([np.nanmean(sums[:, c]) if np.isfinite(sums[:, c]).any() else np.nan for c in range(4)]) / pa_points * 1000
+        for name, o in (('PA_MPJPE_%d' % (n_stages - 1), 0), ('PA_MPVPE_%d' % (n_stages - 1), 2)):
+            l, r = float(mean[o]), float(mean[o + 1])
+            res[name] = {'left': l, 'right': r, 'all': (l + r) / 2}
+        line = ', '.join('{}: left {} mm, right {} mm, AVG {} mm'.format(k, res[k]['left'], res[k]['right'], res[k]['all'])
+                         for k in ('PA_MPJPE_%d' % (n_stages - 1), 'PA_MPVPE_%d' % (n_stages - 1)))
         printed.append(line)
         logged.append(line)
     if not quiet:
@@ -266,7 +292,7 @@ def _count_batches(model, steps):
 
 def fit(model, batches, val_batches=None, output_root='./output', optimizer=None, schedule=None, total_epoch=50, lr=5e-4,
         lr_scheduler='cosine', step='graphed', print_iter=100, draw_iter=100, eval_interval=1, eval_dtype=None, seed=0, max_steps=None,
-        continue_train=None, name='DIR', logger=None, on_step=None, eval_penetration=False):
+        continue_train=None, name='DIR', logger=None, on_step=None, eval_penetration=False, eval_aligned=False):
     """train() of train.py:58-91.  model: a DIR on the GPU, in training mode from here on; batches: TrainBatches of the train split (its
     `rng` is re-seeded per epoch from (seed, epoch)); val_batches: what validate() takes, or None = no validation, no best.pth.
     step: 'graphed' (GraphedTrainStep) | 'eager' (train_step) | 'module' (model(...); sum(loss).backward(); optimizer.step()).
@@ -345,7 +371,7 @@ def fit(model, batches, val_batches=None, output_root='./output', optimizer=None
             logger.info('Save checkpoint to {}'.format(os.path.join(ckpt_dir, 'latest.pth')))
             state['epochs'] += 1
             if val_batches is not None and not epoch % eval_interval:
-                res = validate(model, val_batches, logger=logger, dtype=eval_dtype, penetration=eval_penetration)
+                res = validate(model, val_batches, logger=logger, dtype=eval_dtype, penetration=eval_penetration, aligned=eval_aligned)
                 state['last_val'] = res
                 if res['error'] < state['min_error']:
                     save_checkpoint(os.path.join(ckpt_dir, 'best.pth'), model, optimizer, schedule, epoch)
@@ -405,6 +431,8 @@ def build_parser():
     ap.add_argument('--extra_stages', type=int, default=0)
     ap.add_argument('--eval_penetration', action='store_true', help="add the last stage's mean inter-hand penetration depth and penetration rate to "
                     'the validation lines (best.pth is still chosen by the joint error)')
+    ap.add_argument('--eval_aligned', action='store_true', help="add the last stage's PA-MPJPE and PA-MPVPE (errors after a per-hand similarity "
+                    'alignment) to the validation lines (best.pth is still chosen by the unaligned joint error)')
     return ap
 
 
@@ -430,7 +458,7 @@ def main(argv=None):
                            augment=False, shuffle=False, dense_color=opt.dense_color)
     return fit(model, batches, val, output_root=opt.output_root, total_epoch=opt.total_epoch, lr=opt.lr, lr_scheduler=opt.lr_scheduler,
                step=opt.step, print_iter=opt.print_iter, draw_iter=opt.draw_iter, eval_interval=max(1, opt.eval_interval), seed=opt.seed,
-               max_steps=opt.max_steps, continue_train=opt.continue_train, name=opt.experiment_name, eval_penetration=opt.eval_penetration)
+               max_steps=opt.max_steps, continue_train=opt.continue_train, name=opt.experiment_name, eval_penetration=opt.eval_penetration, eval_aligned=opt.eval_aligned)
 
 
 if __name__ == '__main__':

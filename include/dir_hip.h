@@ -29,7 +29,7 @@ extern "C" {
 #define DIR_E_LAUNCH (-2)   /* hipLaunchKernel / HIP runtime error          */
 #define DIR_E_NODEVICE (-3) /* no gfx950 device visible                     */
 
-#define DIR_ABI_VERSION 43
+#define DIR_ABI_VERSION 44
 
 int dir_abi_version(void);
 const char* dir_last_error(void);
@@ -1132,6 +1132,33 @@ int dir_mesh_penetration(const float* verts_a, const int32_t* faces_a, const flo
 int dir_mesh_intersection_volume(const float* verts_a, const int32_t* faces_a, const float* verts_b, const int32_t* faces_b, int B, int Va,
                                  int Fa, int Vb, int Fb, float h, int max_cells, float* volume, int32_t* n_both, int32_t* cells,
                                  void* stream);
+
+/* ---- aligned evaluation measures: Procrustes-aligned errors, nearest-neighbour distances, threshold counts (csrc/alignmetric.hip) ----
+ * Generic in the point count.  Device pointers, float32 arithmetic, no floating-point atomics; every output of a sample is the same
+ * bits from run to run and in any batch.
+ * dir_procrustes_align fits, per sample, the similarity that maps pd onto gt in the least-squares sense (Umeyama 1991), with
+ * p = pd - mean(pd), g = gt - mean(gt): R the PROPER rotation (det +1, never a reflection) that maximises sum g_i . R p_i, found as Horn's
+ * unit quaternion by Jacobi sweeps; s = sum g_i . R p_i / sum |p_i|^2 with DIR_ALIGN_SCALE in flags, 1 without; t = mean(gt) - s R mean(pd).
+ *   pd, gt     float32 [B,N,3], 3 <= N <= DIR_MESH_MAX_VERTS
+ *   transform  float32 [B,13] or NULL: s, R row-major, t
+ *   aligned    float32 [B,N,3] or NULL: s R pd + t
+ *   err        float32 [B,N]: |aligned - gt|
+ * A sample with a non-finite coordinate or with sum |p_i|^2 = 0 gets NaN in all of its outputs.  Where the maximiser is not unique
+ * (collinear points) one of them is returned: finite, and a proper rotation.
+ * dir_point_set_nn: a float32 [B,Na,3], b float32 [B,Nb,3], 1 <= Na, Nb <= DIR_MESH_MAX_VERTS;
+ *   d_ab  float32 [B,Na]: the distance from each point of a to its nearest point of b (point to point); d_ba float32 [B,Nb]: the reverse.
+ * Non-finite points of the searched set are passed over (+inf when none is left); a non-finite query point gives NaN.
+ * dir_threshold_counts ADDS to counts (int64 [K+1]): counts[k] gains the number of finite err[i] <= thresholds[k], counts[K] the
+ * number of finite values examined.  err float32 [n], 1 <= n <= DIR_ALIGN_MAX_VALUES; thresholds float32 [K], 1 <= K <=
+ * DIR_ALIGN_MAX_THRESHOLDS, in any order.
+ * A null required pointer, B <= 0 or a size outside these limits gives DIR_E_INVALID before any launch. */
+#define DIR_ALIGN_SCALE 1
+#define DIR_ALIGN_MAX_THRESHOLDS 1024
+#define DIR_ALIGN_MAX_VALUES 2147483647LL
+int dir_procrustes_align(const float* pd, const float* gt, int B, int N, int flags, float* transform, float* aligned, float* err,
+                         void* stream);
+int dir_point_set_nn(const float* a, const float* b, int B, int Na, int Nb, float* d_ab, float* d_ba, void* stream);
+int dir_threshold_counts(const float* err, long long n, const float* thresholds, int K, long long* counts, void* stream);
 
 #ifdef __cplusplus
 }
