@@ -128,12 +128,16 @@ class ValMetricsDesc(C.Structure):        # dir_val_metrics_desc
                 ('verts_gt', C.c_void_p * 2), ('sample_sums', C.c_void_p), ('acc', C.c_void_p), ('batches', C.c_void_p)]
 
 
+class FrameDesc(C.Structure):            # dir_frame_desc
+    _fields_ = [('offset', C.c_longlong), ('height', C.c_int32), ('width', C.c_int32), ('row_stride', C.c_longlong)]
+
+
 class RenderLights(C.Structure):         # dir_render_lights
     _fields_ = [('ambient', C.c_float * 3), ('diffuse', C.c_float * 3), ('specular', C.c_float * 3), ('location', C.c_float * 3),
                 ('shininess', C.c_float)]
 
 
-ABI_VERSION = 44         # DIR_ABI_VERSION (include/dir_hip.h)
+ABI_VERSION = 45         # DIR_ABI_VERSION (include/dir_hip.h)
 DT_F32, DT_BF16, DT_F16X3, DT_F16X1, DT_F16X3P, DT_F16X1P, DT_F16 = 0, 1, 3, 4, 5, 6, 7      # DT_F16: f16 STORAGE (round 5)
 CONV_RELU, CONV_PRE_RELU = 1, 2
 
@@ -278,6 +282,9 @@ _SIGNATURES = {
     'dir_procrustes_align': (C.c_int, [_p, _p, _i, _i, _i, _p, _p, _p, _p]),
     'dir_point_set_nn': (C.c_int, [_p, _p, _i, _i, _i, _p, _p, _p]),
     'dir_threshold_counts': (C.c_int, [_p, C.c_longlong, _p, _i, _p, _p]),
+    'dir_crop_matrices_from_boxes': (C.c_int, [_p, _i, C.c_double, _i, _p, _p, _p]),
+    'dir_crop_matrices_from_meshes': (C.c_int, [_p, _p, _p, _p, _p, _i, C.c_double, _i, _p, _p, _p]),
+    'dir_crop_frames': (C.c_int, [_p, C.c_longlong, _p, _p, _p, _i, _i, _p, _p, _p]),
 }
 
 

@@ -9,43 +9,16 @@
 // The fixed-point rules are the published OpenCV algorithm (imgwarp.cpp WarpAffineInvoker + remapBilinear for 8-bit images, filter.cpp
 // Filter2D); they are restated in numpy in tests/helpers/augment_ref.py and are unpinned against the library itself, which is not available.
 #include "dir_common.h"
+#include "warp_fixed.h"
 
 namespace {
 
+using namespace warp;      // the fixed-point coordinate rules, shared with csrc/crop.hip
+
 constexpr int S = 256, HW = S * S;
-constexpr int AB_BITS = 10, AB_SCALE = 1 << AB_BITS, INTER_BITS = 5, INTER_TAB = 1 << INTER_BITS;
-constexpr int ROUND_DELTA = AB_SCALE / INTER_TAB / 2;     // 16: INTER_LINEAR's rounding of the 10-bit coordinate to 5 bits
-constexpr int COEF_BITS = 15;                             // INTER_REMAP_COEF_BITS: the four weights sum to 32768
 constexpr int NJ = 21, NV = 778, NP = NJ + NV;
 
 struct NormArgs { float mean[3], stdv[3]; };
-
-// cv::invertAffineTransform in double, on the float32 matrix of get_affine_mat
-__device__ __forceinline__ void invert_affine(const float* Mf, double* m) {
-#pragma clang fp contract(off)
-    const double M0 = Mf[0], M1 = Mf[1], M2 = Mf[2], M3 = Mf[3], M4 = Mf[4], M5 = Mf[5];
-    double D = M0 * M4 - M1 * M3;
-    D = D != 0. ? 1. / D : 0.;
-    m[0] = M4 * D;
-    m[1] = M1 * -D;
-    m[3] = M3 * -D;
-    m[4] = M0 * D;
-    m[2] = -m[0] * M2 - m[1] * M5;
-    m[5] = -m[3] * M2 - m[4] * M5;
-}
-
-// source position of output pixel (x, y): integer part (sx, sy) and 5-bit fractions (fx, fy) -- AB_BITS = 10 fixed point per row and column
-// (saturate_cast<int> = round half to even), summed, then rounded to INTER_BITS
-__device__ __forceinline__ void warp_coord(const double* m, int x, int y, int& sx, int& sy, int& fx, int& fy) {
-#pragma clang fp contract(off)
-    const int X0 = (int)rint((m[1] * (double)y + m[2]) * (double)AB_SCALE) + ROUND_DELTA;
-    const int Y0 = (int)rint((m[4] * (double)y + m[5]) * (double)AB_SCALE) + ROUND_DELTA;
-    const int ad = (int)rint(m[0] * (double)x * (double)AB_SCALE);
-    const int bd = (int)rint(m[3] * (double)x * (double)AB_SCALE);
-    const int X = (X0 + ad) >> (AB_BITS - INTER_BITS), Y = (Y0 + bd) >> (AB_BITS - INTER_BITS);
-    sx = X >> INTER_BITS; sy = Y >> INTER_BITS;
-    fx = X & (INTER_TAB - 1); fy = Y & (INTER_TAB - 1);
-}
 
 // bilinear tap of one channel; a tap outside the frame reads 0 (BORDER_CONSTANT per tap); `flip` mirrors the source columns
 __device__ __forceinline__ int bilinear_u8(const unsigned char* f, int sx, int sy, const int* w, int c, int flip) {

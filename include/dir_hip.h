@@ -29,7 +29,7 @@ extern "C" {
 #define DIR_E_LAUNCH (-2)   /* hipLaunchKernel / HIP runtime error          */
 #define DIR_E_NODEVICE (-3) /* no gfx950 device visible                     */
 
-#define DIR_ABI_VERSION 44
+#define DIR_ABI_VERSION 45
 
 int dir_abi_version(void);
 const char* dir_last_error(void);
@@ -1159,6 +1159,56 @@ int dir_procrustes_align(const float* pd, const float* gt, int B, int N, int fla
                          void* stream);
 int dir_point_set_nn(const float* a, const float* b, int B, int Na, int Nb, float* d_ab, float* d_ba, void* stream);
 int dir_threshold_counts(const float* err, long long n, const float* thresholds, int K, long long* counts, void* stream);
+
+/* ---- hand crops from full frames: dataset/dataset_utils.py:26-58 (cut_img) for frames of any size (csrc/crop.hip) ----
+ * The crop matrix rule is cut_img's in float64 (inputs converted to double first; every operation rounded on its own).  From the
+ * per-axis Min / Max of a point set, or of the two corners of a tight box (frame pixel positions, OpenCV's convention):
+ *   mid = (Min + Max) / 2,  L = max(Max - Min) / 2 / ratio,  s = (size / 2) / L,  M = [[s, 0, s (L - mid_x)], [0, s, s (L - mid_y)]]
+ * valid = 0, and the matrix is written as zeros, when an input is not finite, L is not finite and positive, s lies outside
+ * [DIR_CROP_MIN_SCALE, DIR_CROP_MAX_SCALE], or one of mid_x - L, mid_x + L, mid_y - L, mid_y + L (the source coordinates of the crop's
+ * corners) exceeds DIR_CROP_MAX_COORD in magnitude -- that bound keeps the 10-bit fixed-point source coordinates inside an int32.
+ * All three entry points allocate nothing and read nothing back.  Device pointers; M is double [B,6] row-major, valid int32 [B].
+ *
+ * dir_crop_matrices_from_boxes: boxes float32 [B,4] = (x0, y0, x1, y1), the tight box around both hands.
+ * dir_crop_matrices_from_meshes, the tracking step: the box of frame t + 1 from the prediction of frame t.  mesh_left / mesh_right float32
+ * [B,778,3], proj_left / proj_right float32 [B,3] = (s, tx, ty) of one stage of DIR.forward, M_prev the matrix frame t was cropped with.
+ * Per vertex: uv = s xy + t in float32 (multiply, then add: utils/utils.py:47-63); crop position c = (uv + 1) size / 2 in double (the
+ * inverse of dataset/interhand.py:229-232); frame position p = (c - (M_prev[2], M_prev[5])) / M_prev[0].  Min / Max over the 1 556
+ * positions go through the rule above.  Minimum and maximum do not depend on the order, so a sample gives the same bits in any batch.
+ * Where the result is invalid (a non-finite position included) M_next = M_prev and valid = 0: the box holds.  M_next may be M_prev.
+ *
+ * dir_crop_frames: out uint8 [B,size,size,3] = cv.warpAffine(frame_b, M_b, (size, size)), INTER_LINEAR, BORDER_CONSTANT 0, for a ragged
+ * batch: `frames` is one packed buffer of frames_bytes bytes holding uint8 BGR images, descs [B] says where each one lies.  M is any
+ * invertible 2x3 matrix, inverted in double as cv.warpAffine does; the fixed-point rules are dir_train_augment_images'.  status int32 [B]
+ * (or NULL) receives, per image, 0 or the reason its crop is all zeros:
+ *   DIR_CROP_INVALID     valid[b] == 0 (valid may be NULL: every matrix is used)
+ *   DIR_CROP_BAD_DESC    height or width outside 1..DIR_CROP_MAX_SIDE, row_stride < 3 width or > DIR_CROP_MAX_STRIDE, offset < 0, or
+ *                        offset + (height - 1) row_stride + 3 width > frames_bytes
+ *   DIR_CROP_BAD_MATRIX  a non-finite entry of the inverse m, or |m0| (size - 1) + |m1| (size - 1) + |m2| > DIR_CROP_MAX_COORD (likewise m3, m4,
+ *                        m5): a source coordinate that far out, whose fixed-point terms could leave an int32
+ * No byte outside [frames, frames + frames_bytes) is read.  size in DIR_CROP_MIN_SIZE..DIR_CROP_MAX_SIZE, B in 1..DIR_CROP_MAX_BATCH
+ * (B = 0 is a no-op); out needs 4-byte alignment. */
+#define DIR_CROP_MIN_SCALE 0.015625 /* 2^-6 */
+#define DIR_CROP_MAX_SCALE 64.0
+#define DIR_CROP_MAX_COORD 1048576.0 /* 2^20 */
+#define DIR_CROP_MIN_SIZE 16
+#define DIR_CROP_MAX_SIZE 1024
+#define DIR_CROP_MAX_BATCH 4096
+#define DIR_CROP_MAX_SIDE 65536
+#define DIR_CROP_MAX_STRIDE 1048576
+#define DIR_CROP_INVALID 1
+#define DIR_CROP_BAD_DESC 2
+#define DIR_CROP_BAD_MATRIX 3
+typedef struct dir_frame_desc {
+    long long offset;       /* of the image's first byte in the packed buffer */
+    int32_t height, width;
+    long long row_stride;   /* bytes from one row to the next, >= 3 width */
+} dir_frame_desc;           /* 24 bytes */
+int dir_crop_matrices_from_boxes(const float* boxes, int B, double ratio, int size, double* M, int32_t* valid, void* stream);
+int dir_crop_matrices_from_meshes(const float* mesh_left, const float* mesh_right, const float* proj_left, const float* proj_right,
+                                  const double* M_prev, int B, double ratio, int size, double* M_next, int32_t* valid, void* stream);
+int dir_crop_frames(const uint8_t* frames, long long frames_bytes, const dir_frame_desc* descs, const double* M, const int32_t* valid,
+                    int B, int size, uint8_t* out, int32_t* status, void* stream);
 
 #ifdef __cplusplus
 }
