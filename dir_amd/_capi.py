@@ -137,7 +137,7 @@ class RenderLights(C.Structure):         # dir_render_lights
                 ('shininess', C.c_float)]
 
 
-ABI_VERSION = 45         # DIR_ABI_VERSION (include/dir_hip.h)
+ABI_VERSION = 46         # DIR_ABI_VERSION (include/dir_hip.h)
 DT_F32, DT_BF16, DT_F16X3, DT_F16X1, DT_F16X3P, DT_F16X1P, DT_F16 = 0, 1, 3, 4, 5, 6, 7      # DT_F16: f16 STORAGE (round 5)
 CONV_RELU, CONV_PRE_RELU = 1, 2
 
@@ -285,6 +285,7 @@ _SIGNATURES = {
     'dir_crop_matrices_from_boxes': (C.c_int, [_p, _i, C.c_double, _i, _p, _p, _p]),
     'dir_crop_matrices_from_meshes': (C.c_int, [_p, _p, _p, _p, _p, _i, C.c_double, _i, _p, _p, _p]),
     'dir_crop_frames': (C.c_int, [_p, C.c_longlong, _p, _p, _p, _i, _i, _p, _p, _p]),
+    'dir_crop_frames_area': (C.c_int, [_p, C.c_longlong, _p, _p, _p, _i, _i, _p, _p, _p, _p]),
 }
 
 

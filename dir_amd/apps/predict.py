@@ -2,7 +2,7 @@
 the GPU) -> DirEngine.forward -> predictions in FRAME pixels.
 
     python -m dir_amd.apps.predict --model CKPT --input DIR|FILES --out DIR [--boxes boxes.json] [--track] [--ratio 0.8] [--bs 32]
-                                   [--stage 2] [--dtype f16|bf16|f32] [--workers 8] [--pictures] [--joints] [--obj]
+                                   [--stage 2] [--dtype f16|bf16|f32] [--workers 8] [--pictures] [--joints] [--obj] [--antialias]
 
 Input: image files (jpg / jpeg / png / bmp) in natural name order, decoded to BGR on the host with Pillow by worker threads that never
 touch the GPU, packed into FrameBatches of at most --bs images.  --boxes: a JSON object {"name": [x0, y0, x1, y1]} keyed by file name (or
@@ -15,6 +15,10 @@ walk --bs at a time): frame 0 takes its box from --boxes (there "sequence/name" 
 a/0.png and b/0.png may start from different boxes) or the whole frame, frame t + 1 the box of frame t's predicted meshes (crop_matrices_from_meshes of stage --stage), chained on the
 device with no host read between frames.  Where a prediction gives no usable box the previous one holds: "tracked": false.
 
+--antialias: a crop that shrinks the frame (a hand box larger than 256 px, as in a 1080p or 4K photo) is resampled with a triangle filter
+as wide as the shrink (crop_frames(antialias=True): Pillow's resize(BILINEAR, box)) instead of four taps per pixel, which skip most of the
+frame's pixels and alias; a crop that does not shrink is unchanged.  The matrices, and with them the way back to frame pixels, are the same.
+
 Output per image, <out>/<stem>.json (in --track with sub-directories <out>/<sequence>/<stem>.json):
   image, width, height   the file and its size
   box                    the tight box the crop was made from (null for a frame whose crop was tracked or held)
@@ -24,6 +28,7 @@ Output per image, <out>/<stem>.json (in --track with sub-directories <out>/<sequ
   left / right           joints_px [21][2] frame pixels, joints_xyz [21][3] metres (root-relative), camera_px {"scale", "trans"}: frame
                          pixel = scale * xy + trans for this hand's vertices and joints
   offset                 the predicted offset between the hands' roots (pd_offset)
+  antialiased            only with --antialias: true where the crop was made with the anti-aliased rule (it shrinks the frame)
 --pictures: <stem>.png, crop | overlay side by side as apps.visualize writes them (--joints as there).  --obj: <stem>.obj, both hands
 placed as vis_utils.prediction_camera places them, faces from the checkpoint.  The last line printed is "N images in T s: R images/s".
 """
@@ -98,11 +103,13 @@ class Tracker(object):
 
     After a step: `M` float64 [B,6] the matrices the crops were made with, `valid` int32 [B] whether a crop could be made, `tracked`
     int32 [B] whether the matrix came from the previous prediction (0 on the first step and where the box was held); all on the
-    device.  The next matrices are made right after the forward, on the device, with no host read."""
+    device.  The next matrices are made right after the forward, on the device, with no host read.  With antialias=True the crops are
+    crop_frames(antialias=True) and `area` int32 [B] says which of them got the anti-aliased rule (None otherwise)."""
 
-    def __init__(self, eng, ratio=0.8, stage=2, size=SIZE, track=True):
+    def __init__(self, eng, ratio=0.8, stage=2, size=SIZE, track=True, antialias=False):
         self.eng, self.ratio, self.stage, self.size, self.track = eng, float(ratio), int(stage), int(size), bool(track)
-        self.M = self.valid = self.tracked = None
+        self.antialias = bool(antialias)
+        self.M = self.valid = self.tracked = self.area = None
         self._next = None
 
     def step(self, batch, boxes=None):
@@ -122,7 +129,10 @@ class Tracker(object):
             M, ok, prev_valid = (x[:B].contiguous() for x in self._next)
             # a held box is as good as it was: the crop stays valid where the previous one was
             self.M, self.tracked, self.valid = M, ok, torch.maximum(ok, prev_valid)
-        crops, status = CR.crop_frames(batch, self.M, self.valid, self.size, return_status=True)
+        if self.antialias:
+            crops, status, self.area = CR.crop_frames(batch, self.M, self.valid, self.size, return_status=True, antialias=True, return_area=True)
+        else:
+            crops, status = CR.crop_frames(batch, self.M, self.valid, self.size, return_status=True)
         self.valid = self.valid * (status == 0).to(torch.int32)            # a crop the kernel refused is black: the image is not valid
         outs = self.eng.forward(crops, want_proj_feat=False)
         if self.track:
@@ -136,6 +146,8 @@ def _records(paths, batch, boxes_used, tr, outs, stage, keep_stage):
     o = outs[stage]
     M = tr.M
     t = {'M': M, 'valid': tr.valid, 'tracked': tr.tracked, 'offset': o['pd_offset'].float()}
+    if tr.area is not None:
+        t['area'] = tr.area
     for s in SIDES:
         t['px_' + s] = CR.to_frame_pixels(o['pd_joint_uv_' + s].float(), M, tr.size)
         t['xyz_' + s] = o['pd_joint_xyz_' + s].float()
@@ -157,6 +169,8 @@ def _records(paths, batch, boxes_used, tr, outs, stage, keep_stage):
             r[s] = {'joints_px': num(h['px_' + s][j].tolist()), 'joints_xyz': num(h['xyz_' + s][j].tolist()),
                     'camera_px': {'scale': num(float(h['sc_' + s][j])), 'trans': num(h['tr_' + s][j].tolist())}}
         r['offset'] = num(h['offset'][j].reshape(-1).tolist())
+        if 'area' in h:
+            r['antialiased'] = bool(h['area'][j])
         if keep_stage:
             r['stage'] = {k: h[k][j] for k in h if k.startswith('pd_')}
         recs.append(r)
@@ -184,11 +198,11 @@ def lockstep_groups(seqs, bs):
     return [[[(g0 + i, item) for i, item in st] for st in lockstep(seqs[g0:g0 + bs])] for g0 in range(0, len(seqs), bs)]
 
 
-def _walk(eng, steps, load, names, box_of, ratio, stage, track, keep_stage):
+def _walk(eng, steps, load, names, box_of, ratio, stage, track, keep_stage, antialias=False):
     """the one loop: per step FrameBatch -> Tracker.step -> records.  load(k) -> the decoded frames of step k; box_of(entry, h, w) -> the
     box of a step entry.  Yields (entries, records, crops, outs) with the device tensors of that step."""
     from ..utils import crop as CR
-    tr = Tracker(eng, ratio, stage, track=track)
+    tr = Tracker(eng, ratio, stage, track=track, antialias=antialias)
     for k, st in enumerate(steps):
         batch = CR.FrameBatch(load(k))
         used = [box_of(e, h, w) for e, (h, w) in zip(st, batch.sizes)] if (not track or k == 0) else None
@@ -196,7 +210,7 @@ def _walk(eng, steps, load, names, box_of, ratio, stage, track, keep_stage):
         yield st, _records([names(e) for e in st], batch, used, tr, outs, stage, keep_stage), crops, outs
 
 
-def predict(eng, frames, boxes=None, ratio=0.8, stage=2, bs=32, track=False, keep_stage=False, keep_crops=False):
+def predict(eng, frames, boxes=None, ratio=0.8, stage=2, bs=32, track=False, keep_stage=False, keep_crops=False, antialias=False):
     """The loop behind the command, on decoded frames.
 
     frames: without `track` a list of uint8 BGR arrays [H,W,3] of any sizes, taken `bs` at a time; with `track` a list of sequences (each
@@ -204,7 +218,8 @@ def predict(eng, frames, boxes=None, ratio=0.8, stage=2, bs=32, track=False, kee
     than `bs` sequences walk `bs` at a time, one group after the other.
     boxes: one (x0, y0, x1, y1) or None per image (with `track` per sequence: the box of its frame 0); None: whole frames.
     -> a list of records (the JSON fields; with `track` one list per sequence), each with 'crop' (uint8 [256,256,3]) when keep_crops and
-    'stage' (the stage's meshes, projections and joint uv as numpy arrays) when keep_stage."""
+    'stage' (the stage's meshes, projections and joint uv as numpy arrays) when keep_stage.  antialias: anti-aliased crops where a crop
+    shrinks its frame; every record then has 'antialiased'."""
     if track:
         groups = lockstep_groups([list(s) for s in frames], bs)
         out = [[] for _ in frames]
@@ -215,7 +230,8 @@ def predict(eng, frames, boxes=None, ratio=0.8, stage=2, bs=32, track=False, kee
     def box_of(e, h, w):
         return [float(v) for v in boxes[e[0]]] if boxes is not None and boxes[e[0]] is not None else [0.0, 0.0, w - 1.0, h - 1.0]
     for steps in groups:
-        for st, recs, crops, outs in _walk(eng, steps, lambda k: [f for _, f in steps[k]], lambda e: str(e[0]), box_of, ratio, stage, track, keep_stage):
+        for st, recs, crops, outs in _walk(eng, steps, lambda k: [f for _, f in steps[k]], lambda e: str(e[0]), box_of, ratio, stage, track, keep_stage,
+                                            antialias):
             ch = crops.cpu().numpy() if keep_crops else None
             for j, ((i, _), r) in enumerate(zip(st, recs)):
                 if keep_crops:
@@ -228,7 +244,7 @@ def predict(eng, frames, boxes=None, ratio=0.8, stage=2, bs=32, track=False, kee
 
 
 def run(eng, sequences, out_dir, boxes=None, ratio=0.8, stage=2, bs=32, track=False, workers=8, pictures=False, joints=False, obj=False,
-        renderer=None, faces=None):
+        renderer=None, faces=None, antialias=False):
     """files -> files.  sequences: [[paths]] (one list without `track`).  -> (images, seconds, seconds of them spent waiting for decoded
     frames).  Two steps are decoded ahead of the GPU by at most 16 threads; the files are written by 8 more.  With `track`, more than `bs`
     sequences walk `bs` at a time, so that no batch holds more than `bs` images."""
@@ -262,7 +278,8 @@ def run(eng, sequences, out_dir, boxes=None, ratio=0.8, stage=2, bs=32, track=Fa
                 frames = [f.result() for f in ahead.pop(k)]
                 wait[0] += time.perf_counter() - w0
                 return frames
-            for st, recs, crops, outs in _walk(eng, steps, load, lambda e: e[1], lambda e, h, w: box_for(boxes, e[1], h, w), ratio, stage, track, False):
+            for st, recs, crops, outs in _walk(eng, steps, load, lambda e: e[1], lambda e, h, w: box_for(boxes, e[1], h, w), ratio, stage, track, False,
+                                            antialias):
                 if pictures:
                     over = V.overlay_predictions(outs[stage], crops, renderer)
                     if joints:
@@ -306,6 +323,7 @@ def main(argv=None):
     ap.add_argument('--pictures', action='store_true', help='write <stem>.png: crop | overlay')
     ap.add_argument('--joints', action='store_true', help='draw the predicted 2-D joints on the overlay')
     ap.add_argument('--obj', action='store_true', help='write <stem>.obj: both predicted hands in one frame')
+    ap.add_argument('--antialias', action='store_true', help='anti-aliased crops where the crop shrinks the frame (hand boxes larger than 256 px)')
     opt = ap.parse_args(argv)
     if opt.bs < 1:
         ap.error('--bs must be at least 1')
@@ -327,7 +345,7 @@ def main(argv=None):
             renderer = V.mano_two_hands_shaded_renderer(right_faces=mano['right'].get_faces(), dense_color=np.zeros((V.NV_HAND, 3)), img_size=SIZE,
                                                         device=eng.device)
     n, sec, wait = run(eng, sequences, opt.out, boxes, opt.ratio, opt.stage, opt.bs, opt.track, opt.workers, opt.pictures, opt.joints, opt.obj,
-                       renderer, faces)
+                       renderer, faces, opt.antialias)
     print('waited %.2f s of them for decoded frames' % wait)
     print('%d images in %.1f s: %.0f images/s' % (n, sec, n / max(sec, 1e-9)))
     return n

@@ -1,5 +1,5 @@
-"""Hand crops from full frames on the GPU: csrc/crop.hip through dir_crop_matrices_from_boxes, dir_crop_matrices_from_meshes and
-dir_crop_frames.  The reference crops in one place only, dataset/dataset_utils.py:26-58 (cut_img, called by prepare_data.py:153-154 with the
+"""Hand crops from full frames on the GPU: csrc/crop.hip through dir_crop_matrices_from_boxes, dir_crop_matrices_from_meshes,
+dir_crop_frames and dir_crop_frames_area.  The reference crops in one place only, dataset/dataset_utils.py:26-58 (cut_img, called by prepare_data.py:153-154 with the
 ground-truth vertices and ratio 0.8); this is the same crop for frames of any size, from a box or from the previous frame's prediction,
 and the way back from crop coordinates to frame pixels.  The rules are written out in include/dir_hip.h and restated in float64 numpy by
 tests/helpers/crop_ref.py.
@@ -7,7 +7,8 @@ tests/helpers/crop_ref.py.
   crop_matrices_from_boxes    boxes [B,4] (x0, y0, x1, y1) -> (M float64 [B,6], valid int32 [B]), device tensors
   crop_matrices_from_meshes   one stage of DirEngine.forward + the matrices of its crops -> (M_next, valid): the tracking step
   FrameBatch                  HxWx3 uint8 BGR arrays of any sizes packed into one pinned buffer with their descriptors; one H2D copy
-  crop_frames                 FrameBatch + M -> uint8 [B,size,size,3] = cv.warpAffine(frame, M, (size, size)), what DirEngine.forward takes
+  crop_frames                 FrameBatch + M -> uint8 [B,size,size,3] = cv.warpAffine(frame, M, (size, size)), what DirEngine.forward takes;
+                              antialias=True: where M shrinks the frame, Pillow's resize(BILINEAR, box) instead (no aliasing)
   to_frame_pixels             normalised crop uv [B,N,2] -> frame pixels
   frame_camera                (s, t) of uv = s xy + t -> (scale_px, trans_px) with frame pixel = scale_px xy + trans_px
 """
@@ -151,13 +152,21 @@ class FrameBatch(object):
         return self._dev
 
 
-def crop_frames(batch, M, valid=None, size=256, return_status=False):
+def crop_frames(batch, M, valid=None, size=256, return_status=False, antialias=False, return_area=False):
     """dir_crop_frames: batch a FrameBatch, M float64 cuda [B,6] (OpenCV's convention: crop position = M * frame position), valid int32
     cuda [B] or None -> uint8 cuda [B,size,size,3], byte for byte cv.warpAffine(frame, M, (size, size)) with INTER_LINEAR and a zero
     border.  An image whose `valid` is 0, whose descriptor reaches outside the buffer or whose matrix sends a crop pixel beyond 2^20 px
-    gives an all-zero crop; with return_status -> (crops, status int32 [B]: 0 or STATUS_INVALID / STATUS_BAD_DESC / STATUS_BAD_MATRIX)."""
+    gives an all-zero crop; with return_status -> (crops, status int32 [B]: 0 or STATUS_INVALID / STATUS_BAD_DESC / STATUS_BAD_MATRIX).
+
+    antialias=True (dir_crop_frames_area): an image whose matrix shrinks the frame (no rotation, shear or mirror, both scales positive,
+    the smaller one below 1) is resampled with a triangle filter as wide as the shrink -- byte for byte Pillow's
+    Image.resize((size, size), BILINEAR, box) on the box the matrix cuts out, with the same zero border -- and every other image is the
+    crop above, byte for byte.  A shrinking scale below 2^-6 is STATUS_BAD_MATRIX.  With return_area the tuple ends with area int32 [B]:
+    1 where the anti-aliased rule was used.  -> crops, or (crops[, status][, area])."""
     if not isinstance(batch, FrameBatch):
         raise ValueError('crop_frames: batch must be a FrameBatch')
+    if return_area and not antialias:
+        raise ValueError('crop_frames: return_area needs antialias=True')
     _capi.require_cuda(M, valid)
     B, dev = len(batch), M.device
     _check_common('crop_frames', B, 1.0, size)
@@ -168,10 +177,17 @@ def crop_frames(batch, M, valid=None, size=256, return_status=False):
     out = torch.empty(B, size, size, 3, dtype=torch.uint8, device=dev)
     status = torch.empty(B, dtype=torch.int32, device=dev)
     P = _capi.ptr
+    descs = ctypes.c_void_p(buf.data_ptr() + batch._desc_off)
+    area = torch.empty(B, dtype=torch.int32, device=dev) if return_area else None
     with torch.cuda.device(dev):
-        _capi.check(_capi.lib().dir_crop_frames(P(buf), batch.nbytes, ctypes.c_void_p(buf.data_ptr() + batch._desc_off), P(M), P(valid), B, size,
-                                                P(out), P(status), _capi.stream_ptr()), 'dir_crop_frames')
-    return (out, status) if return_status else out
+        if antialias:
+            _capi.check(_capi.lib().dir_crop_frames_area(P(buf), batch.nbytes, descs, P(M), P(valid), B, size, P(out), P(status), P(area),
+                                                         _capi.stream_ptr()), 'dir_crop_frames_area')
+        else:
+            _capi.check(_capi.lib().dir_crop_frames(P(buf), batch.nbytes, descs, P(M), P(valid), B, size, P(out), P(status), _capi.stream_ptr()),
+                        'dir_crop_frames')
+    res = (out,) + ((status,) if return_status else ()) + ((area,) if return_area else ())
+    return res if len(res) > 1 else out
 
 
 def to_frame_pixels(uv, M, size=256):

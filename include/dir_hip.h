@@ -29,7 +29,7 @@ extern "C" {
 #define DIR_E_LAUNCH (-2)   /* hipLaunchKernel / HIP runtime error          */
 #define DIR_E_NODEVICE (-3) /* no gfx950 device visible                     */
 
-#define DIR_ABI_VERSION 45
+#define DIR_ABI_VERSION 46
 
 int dir_abi_version(void);
 const char* dir_last_error(void);
@@ -1187,7 +1187,26 @@ int dir_threshold_counts(const float* err, long long n, const float* thresholds,
  *   DIR_CROP_BAD_MATRIX  a non-finite entry of the inverse m, or |m0| (size - 1) + |m1| (size - 1) + |m2| > DIR_CROP_MAX_COORD (likewise m3, m4,
  *                        m5): a source coordinate that far out, whose fixed-point terms could leave an int32
  * No byte outside [frames, frames + frames_bytes) is read.  size in DIR_CROP_MIN_SIZE..DIR_CROP_MAX_SIZE, B in 1..DIR_CROP_MAX_BATCH
- * (B = 0 is a no-op); out needs 4-byte alignment. */
+ * (B = 0 is a no-op); out needs 4-byte alignment.
+ *
+ * dir_crop_frames_area: dir_crop_frames with anti-aliasing where the crop shrinks the frame.  Arguments, statuses and the black crop of a
+ * refused image are dir_crop_frames'; `area` int32 [B] (or NULL) receives 1 for the images that got the rule below, else 0.  Two launches,
+ * no host read, no workspace: the matrices may come straight from dir_crop_matrices_from_meshes.  An image gets the same bytes in any
+ * batch and at any position of it.
+ *   Which images: M is "shrinking" when M[1] == 0 and M[3] == 0, M[0] > 0 and M[4] > 0, and min(M[0], M[4]) < 1.  Every other usable
+ *   matrix (a scale >= 1, a rotation, a shear, a mirror) gives exactly dir_crop_frames' bytes.  A shrinking matrix that dir_crop_frames
+ *   would refuse, or whose min(M[0], M[4]) < DIR_CROP_MIN_SCALE, is DIR_CROP_BAD_MATRIX: that bound keeps a window at 2 * 64 + 1 taps.
+ *   The rule is Pillow's Image.resize((size, size), BILINEAR, box) -- libImaging/Resample.c: precompute_coeffs and normalize_coeffs_8bpc with
+ *   PRECISION_BITS = 22, horizontal pass, then vertical pass -- on the box the matrix cuts out of the frame, without Pillow's clamping of
+ *   the window to the image.  Per axis (x shown; s = M[0], t = M[2]; y: M[4], M[5]), in float64, every operation rounded on its own:
+ *     in0 = 0.5 - (t + 0.5) / s,  in1 = in0 + size / s          the crop's edges in frame pixels (pixel k covers [k, k + 1))
+ *     scale = (in1 - in0) / size,  fs = max(scale, 1),  support = fs
+ *   and per output position u:
+ *     c = in0 + (u + 0.5) scale,  xmin = floor(c - support + 0.5),  xmax = floor(c + support + 0.5),  taps x = xmin .. xmax - 1
+ *     k[x] = max(0, 1 - |(x - c + 0.5) / fs|),  ww = the sum of k in tap order,  K[x] = (int)(k[x] / ww * 2^22 + 0.5)
+ *   A tap outside the frame reads 0 and keeps its weight (the zero border of dir_crop_frames; Pillow on a frame padded with zeros); it is
+ *   never loaded.  Horizontal pass: tmp = clip8((2^21 + sum K_x src) >> 22), stored as uint8 -- the rounding between the passes is part of
+ *   the rule; vertical pass: the same over tmp with the rows' coefficients.  The integer sums are exact in any order. */
 #define DIR_CROP_MIN_SCALE 0.015625 /* 2^-6 */
 #define DIR_CROP_MAX_SCALE 64.0
 #define DIR_CROP_MAX_COORD 1048576.0 /* 2^20 */
@@ -1209,6 +1228,8 @@ int dir_crop_matrices_from_meshes(const float* mesh_left, const float* mesh_righ
                                   const double* M_prev, int B, double ratio, int size, double* M_next, int32_t* valid, void* stream);
 int dir_crop_frames(const uint8_t* frames, long long frames_bytes, const dir_frame_desc* descs, const double* M, const int32_t* valid,
                     int B, int size, uint8_t* out, int32_t* status, void* stream);
+int dir_crop_frames_area(const uint8_t* frames, long long frames_bytes, const dir_frame_desc* descs, const double* M, const int32_t* valid,
+                         int B, int size, uint8_t* out, int32_t* status, int32_t* area, void* stream);
 
 #ifdef __cplusplus
 }
