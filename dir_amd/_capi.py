@@ -132,12 +132,16 @@ class FrameDesc(C.Structure):            # dir_frame_desc
     _fields_ = [('offset', C.c_longlong), ('height', C.c_int32), ('width', C.c_int32), ('row_stride', C.c_longlong)]
 
 
+class OneEuroSegment(C.Structure):       # dir_one_euro_segment
+    _fields_ = [('n_points', C.c_int32), ('dims', C.c_int32), ('speed_scale', C.c_float)]
+
+
 class RenderLights(C.Structure):         # dir_render_lights
     _fields_ = [('ambient', C.c_float * 3), ('diffuse', C.c_float * 3), ('specular', C.c_float * 3), ('location', C.c_float * 3),
                 ('shininess', C.c_float)]
 
 
-ABI_VERSION = 46         # DIR_ABI_VERSION (include/dir_hip.h)
+ABI_VERSION = 47         # DIR_ABI_VERSION (include/dir_hip.h)
 DT_F32, DT_BF16, DT_F16X3, DT_F16X1, DT_F16X3P, DT_F16X1P, DT_F16 = 0, 1, 3, 4, 5, 6, 7      # DT_F16: f16 STORAGE (round 5)
 CONV_RELU, CONV_PRE_RELU = 1, 2
 
@@ -286,6 +290,8 @@ _SIGNATURES = {
     'dir_crop_matrices_from_meshes': (C.c_int, [_p, _p, _p, _p, _p, _i, C.c_double, _i, _p, _p, _p]),
     'dir_crop_frames': (C.c_int, [_p, C.c_longlong, _p, _p, _p, _i, _i, _p, _p, _p]),
     'dir_crop_frames_area': (C.c_int, [_p, C.c_longlong, _p, _p, _p, _i, _i, _p, _p, _p, _p]),
+    'dir_one_euro_state_bytes': (C.c_longlong, [_i, _i, C.POINTER(C.c_longlong)]),
+    'dir_one_euro_step': (C.c_int, [_p, _p, _i, C.POINTER(OneEuroSegment), _i, C.c_double, C.c_double, C.c_double, C.c_double, _i, _p, _p, _p, _p]),
 }
 
 
@@ -297,7 +303,8 @@ PROFILE = None
 _pending = {}
 _NO_PROFILE = ('dir_conv2d_as_supported', 'dir_residual_chain_supported', 'dir_abi_version', 'dir_bn_one_launch_status', 'dir_bn_one_launch_enable', 'dir_last_error', 'dir_device_info', 'dir_launch_log_reset', 'dir_launch_log_get', 'dir_launch_log_note',
                'dir_bone_fusion_scratch_bytes', 'dir_dense_losses_workspace_bytes', 'dir_dense_losses_backward_workspace_bytes',
-               'dir_gemm_f32_splitk_workspace_bytes', 'dir_bn_train_workspace_bytes', 'dir_bn_sync_workspace_bytes', 'dir_bn_frozen_workspace_bytes', 'dir_jpeg_planes_bytes', 'dir_render_workspace_bytes', 'dir_render_adjacency_bytes', 'dir_render_shaded_workspace_bytes', 'dir_colsum_workspace_bytes', 'dir_conv2d_wgrad_workspace_bytes', 'dir_conv2d_wgrad_f16x3_workspace_bytes')
+               'dir_gemm_f32_splitk_workspace_bytes', 'dir_bn_train_workspace_bytes', 'dir_bn_sync_workspace_bytes', 'dir_bn_frozen_workspace_bytes', 'dir_jpeg_planes_bytes', 'dir_render_workspace_bytes', 'dir_render_adjacency_bytes', 'dir_render_shaded_workspace_bytes', 'dir_colsum_workspace_bytes', 'dir_conv2d_wgrad_workspace_bytes', 'dir_conv2d_wgrad_f16x3_workspace_bytes',
+               'dir_one_euro_state_bytes')
 
 
 def annotate(**kw):

@@ -3,6 +3,7 @@ the GPU) -> DirEngine.forward -> predictions in FRAME pixels.
 
     python -m dir_amd.apps.predict --model CKPT --input DIR|FILES --out DIR [--boxes boxes.json] [--track] [--ratio 0.8] [--bs 32]
                                    [--stage 2] [--dtype f16|bf16|f32] [--workers 8] [--pictures] [--joints] [--obj] [--antialias]
+                                   [--smooth] [--smooth_box] [--fps 30] [--min_cutoff 1.0] [--beta 0.007] [--d_cutoff 1.0]
 
 Input: image files (jpg / jpeg / png / bmp) in natural name order, decoded to BGR on the host with Pillow by worker threads that never
 touch the GPU, packed into FrameBatches of at most --bs images.  --boxes: a JSON object {"name": [x0, y0, x1, y1]} keyed by file name (or
@@ -19,6 +20,19 @@ device with no host read between frames.  Where a prediction gives no usable box
 as wide as the shrink (crop_frames(antialias=True): Pillow's resize(BILINEAR, box)) instead of four taps per pixel, which skip most of the
 frame's pixels and alias; a crop that does not shrink is unchanged.  The matrices, and with them the way back to frame pixels, are the same.
 
+--smooth (with --track): every frame's prediction goes through the One-Euro filter (utils/smooth.py, csrc/smooth.hip: one launch per frame
+over all streams of all sequences, state on the device, no host read) in FRAME space: meshes, 3-D joints and the offset in metres, 2-D
+joints and cameras in frame pixels.  left / right / offset then hold the filtered values and "raw" what they are without the flag, bit for
+bit: the crops and the forwards are the same.  --pictures, --joints and --obj draw the filtered prediction mapped back into the crop.  A
+frame without a valid crop, or with a non-finite prediction, passes through unchanged (nulls stay nulls) and the filter takes the next
+usable frame with dt = frames since the last one / --fps; after more than round(--fps) such frames it starts again.  --fps, --min_cutoff,
+--beta, --d_cutoff are the filter's parameters; the defaults are the paper's (Casiez et al. 2012) and are NOT tuned on real video.  At the
+end <out>/jitter.json (<out>/<sequence>/jitter.json with sub-directories) holds, per stream, the mean second difference per point per frame
+of the raw and of the filtered values, and a line before the last one prints their means in mm/frame^2 and px/frame^2.
+--smooth_box (with --track, separate from --smooth, off by default): the next tracked box (its centre and half side) goes through a filter
+of its own before the next crop is made, on the device; a first box and a held box are unchanged.  This changes the crops, and with them
+every prediction after frame 1.  These flags without --track are an error.
+
 Output per image, <out>/<stem>.json (in --track with sub-directories <out>/<sequence>/<stem>.json):
   image, width, height   the file and its size
   box                    the tight box the crop was made from (null for a frame whose crop was tracked or held)
@@ -29,6 +43,8 @@ Output per image, <out>/<stem>.json (in --track with sub-directories <out>/<sequ
                          pixel = scale * xy + trans for this hand's vertices and joints
   offset                 the predicted offset between the hands' roots (pd_offset)
   antialiased            only with --antialias: true where the crop was made with the anti-aliased rule (it shrinks the frame)
+  smoothed, raw          only with --smooth: true, and {"left", "right", "offset"} as they are without the flag
+  box_smoothed           only with --smooth_box: true where this frame's matrix went through the box filter
 --pictures: <stem>.png, crop | overlay side by side as apps.visualize writes them (--joints as there).  --obj: <stem>.obj, both hands
 placed as vis_utils.prediction_camera places them, faces from the checkpoint.  The last line printed is "N images in T s: R images/s".
 """
@@ -104,13 +120,26 @@ class Tracker(object):
     After a step: `M` float64 [B,6] the matrices the crops were made with, `valid` int32 [B] whether a crop could be made, `tracked`
     int32 [B] whether the matrix came from the previous prediction (0 on the first step and where the box was held); all on the
     device.  The next matrices are made right after the forward, on the device, with no host read.  With antialias=True the crops are
-    crop_frames(antialias=True) and `area` int32 [B] says which of them got the anti-aliased rule (None otherwise)."""
+    crop_frames(antialias=True) and `area` int32 [B] says which of them got the anti-aliased rule (None otherwise).
 
-    def __init__(self, eng, ratio=0.8, stage=2, size=SIZE, track=True, antialias=False):
+    smooth (True, or a dict of utils.smooth.OneEuro's parameters; needs track): after every forward the stage goes through a
+    PredictionSmoother sized by the first step; `smoothed` is its result (frame space) and drawn(outs) the stage dict to draw.  smooth_box
+    (likewise): the next matrices go through smooth_matrices before the next crop; `box_smoothed` int32 [B] says which of the current
+    matrices did.  Neither reads anything back."""
+
+    def __init__(self, eng, ratio=0.8, stage=2, size=SIZE, track=True, antialias=False, smooth=None, smooth_box=None):
         self.eng, self.ratio, self.stage, self.size, self.track = eng, float(ratio), int(stage), int(size), bool(track)
         self.antialias = bool(antialias)
         self.M = self.valid = self.tracked = self.area = None
         self._next = None
+        self.smooth, self.smooth_box = (None if not p else ({} if p is True else dict(p)) for p in (smooth, smooth_box))
+        if (self.smooth is not None or self.smooth_box is not None) and not self.track:
+            raise ValueError('Tracker: smooth and smooth_box need track=True')
+        self.smoother = self.box_filter = self.smoothed = self.box_smoothed = self._box_updated = None
+
+    def drawn(self, outs):
+        """the stage dict to draw: the smoothed prediction in the current crop, or the stage itself"""
+        return self.smoother.crop_stage() if self.smoother is not None else outs[self.stage]
 
     def step(self, batch, boxes=None):
         import torch
@@ -123,12 +152,16 @@ class Tracker(object):
             b = torch.as_tensor(np.asarray(boxes, np.float32).reshape(B, 4)).to(dev)
             self.M, self.valid = CR.crop_matrices_from_boxes(b, self.ratio, self.size)
             self.tracked = torch.zeros(B, dtype=torch.int32, device=dev)
+            if self.smooth_box is not None:
+                self.box_smoothed = torch.zeros(B, dtype=torch.int32, device=dev)
         else:
             if self._next[0].shape[0] < B:
                 raise ValueError('Tracker.step: %d frames after %d: sequences may end (from the tail of the batch), not begin' % (B, self._next[0].shape[0]))
             M, ok, prev_valid = (x[:B].contiguous() for x in self._next)
             # a held box is as good as it was: the crop stays valid where the previous one was
             self.M, self.tracked, self.valid = M, ok, torch.maximum(ok, prev_valid)
+            if self.smooth_box is not None:
+                self.box_smoothed = (self._box_updated[:B] == 1).to(torch.int32)
         if self.antialias:
             crops, status, self.area = CR.crop_frames(batch, self.M, self.valid, self.size, return_status=True, antialias=True, return_area=True)
         else:
@@ -136,7 +169,18 @@ class Tracker(object):
         self.valid = self.valid * (status == 0).to(torch.int32)            # a crop the kernel refused is black: the image is not valid
         outs = self.eng.forward(crops, want_proj_feat=False)
         if self.track:
-            self._next = CR.crop_matrices_from_meshes(outs[self.stage], self.M, self.ratio, self.size) + (self.valid,)
+            M_next, ok = CR.crop_matrices_from_meshes(outs[self.stage], self.M, self.ratio, self.size)
+            if self.smooth_box is not None:
+                from ..utils import smooth as SM
+                if self.box_filter is None:
+                    self.box_filter = SM.box_filter(B, device=dev, **self.smooth_box)
+                M_next, self._box_updated = SM.smooth_matrices(self.box_filter, M_next, ok, self.size)
+            self._next = (M_next, ok, self.valid)
+        if self.smooth is not None:
+            from ..utils import smooth as SM
+            if self.smoother is None:
+                self.smoother = SM.PredictionSmoother(B, self.size, device=dev, **self.smooth)
+            self.smoothed = self.smoother.step(outs[self.stage], self.M, self.valid)
         return crops, outs
 
 
@@ -155,6 +199,15 @@ def _records(paths, batch, boxes_used, tr, outs, stage, keep_stage):
     if keep_stage:
         for k in ('pd_mesh_xyz_left', 'pd_mesh_xyz_right', 'pd_proj_left', 'pd_proj_right', 'pd_joint_uv_left', 'pd_joint_uv_right'):
             t[k] = o[k].float()
+    fr = tr.smoothed if tr.smooth is not None else None
+    if fr is not None:
+        t['s_offset'] = fr['offset']
+        for s in SIDES:
+            t['s_px_' + s], t['s_xyz_' + s], t['s_cam_' + s] = fr['joints_px_' + s], fr['joint_xyz_' + s], fr['camera_px_' + s]
+        if keep_stage:
+            t.update(('s_' + k, v) for k, v in tr.smoother.crop_stage().items())
+    if tr.box_smoothed is not None:
+        t['box_smoothed'] = tr.box_smoothed
     h = {k: v.cpu().numpy() for k, v in t.items()}
 
     def num(a):
@@ -169,10 +222,21 @@ def _records(paths, batch, boxes_used, tr, outs, stage, keep_stage):
             r[s] = {'joints_px': num(h['px_' + s][j].tolist()), 'joints_xyz': num(h['xyz_' + s][j].tolist()),
                     'camera_px': {'scale': num(float(h['sc_' + s][j])), 'trans': num(h['tr_' + s][j].tolist())}}
         r['offset'] = num(h['offset'][j].reshape(-1).tolist())
+        if fr is not None:                                                # the fields above are today's: they move to "raw"
+            r['raw'] = {k: r[k] for k in SIDES + ('offset',)}
+            for s in SIDES:
+                r[s] = {'joints_px': num(h['s_px_' + s][j].tolist()), 'joints_xyz': num(h['s_xyz_' + s][j].tolist()),
+                        'camera_px': {'scale': num(float(h['s_cam_' + s][j][0])), 'trans': num(h['s_cam_' + s][j][1:3].tolist())}}
+            r['offset'] = num(h['s_offset'][j].reshape(-1).tolist())
+            r['smoothed'] = True
+        if 'box_smoothed' in h:
+            r['box_smoothed'] = bool(h['box_smoothed'][j])
         if 'area' in h:
             r['antialiased'] = bool(h['area'][j])
         if keep_stage:
             r['stage'] = {k: h[k][j] for k in h if k.startswith('pd_')}
+            if fr is not None:
+                r['stage_smoothed'] = {k[2:]: h[k][j] for k in h if k.startswith('s_pd_')}
         recs.append(r)
     return recs
 
@@ -198,19 +262,47 @@ def lockstep_groups(seqs, bs):
     return [[[(g0 + i, item) for i, item in st] for st in lockstep(seqs[g0:g0 + bs])] for g0 in range(0, len(seqs), bs)]
 
 
-def _walk(eng, steps, load, names, box_of, ratio, stage, track, keep_stage, antialias=False):
+def _walk(eng, steps, load, names, box_of, ratio, stage, track, keep_stage, antialias=False, smooth=None, smooth_box=None):
     """the one loop: per step FrameBatch -> Tracker.step -> records.  load(k) -> the decoded frames of step k; box_of(entry, h, w) -> the
-    box of a step entry.  Yields (entries, records, crops, outs) with the device tensors of that step."""
+    box of a step entry.  Yields (entries, records, crops, outs, tracker) with the device tensors of that step."""
     from ..utils import crop as CR
-    tr = Tracker(eng, ratio, stage, track=track, antialias=antialias)
+    tr = Tracker(eng, ratio, stage, track=track, antialias=antialias, smooth=smooth, smooth_box=smooth_box)
     for k, st in enumerate(steps):
         batch = CR.FrameBatch(load(k))
         used = [box_of(e, h, w) for e, (h, w) in zip(st, batch.sizes)] if (not track or k == 0) else None
         crops, outs = tr.step(batch, used)
-        yield st, _records([names(e) for e in st], batch, used, tr, outs, stage, keep_stage), crops, outs
+        yield st, _records([names(e) for e in st], batch, used, tr, outs, stage, keep_stage), crops, outs, tr
 
 
-def predict(eng, frames, boxes=None, ratio=0.8, stage=2, bs=32, track=False, keep_stage=False, keep_crops=False, antialias=False):
+def sequence_jitter(tr, steps):
+    """after a walk with smooth: one host read -> {sequence index: the jitter of its row as JSON fields}.  Per stream (PredictionSmoother's
+    order) the mean |second difference| per point per frame of the raw and of the filtered values -- metres for mesh_xyz, joint_xyz and offset, frame
+    pixels for joints_px; camera_px mixes pixels per metre and pixels -- over `frames` frames (every third and later of consecutive updates)"""
+    from ..utils import smooth as SM
+    j = tr.smoother.jitter()
+
+    def num(a):
+        return [v if np.isfinite(v) else None for v in a.tolist()]
+    return {i: {'streams': j['streams'], 'points': [p for _, p, _, _ in SM.STREAMS], 'frames': int(j['frames'][row]), 'raw': num(j['raw'][row]),
+                'filtered': num(j['filtered'][row]), 'sums': j['sums'][row].tolist()} for row, (i, _) in enumerate(steps[0])}
+
+
+def jitter_summary(jitters):
+    """[sequence_jitter records] -> ((raw, filtered) in mm/frame^2 over the metric streams, (raw, filtered) in px/frame^2 over joints_px),
+    means per point per frame over all sequences; NaN when no frame was counted"""
+    mm, px = np.zeros(3), np.zeros(3)
+    for j in jitters:
+        for name, p, (raw, fil) in zip(j['streams'], j['points'], j['sums']):
+            if name.startswith('camera_px'):
+                continue
+            acc = px if name.startswith('joints_px') else mm
+            acc += (raw, fil, p * j['frames'])
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return tuple(mm[:2] / mm[2] * 1000.0), tuple(px[:2] / px[2])
+
+
+def predict(eng, frames, boxes=None, ratio=0.8, stage=2, bs=32, track=False, keep_stage=False, keep_crops=False, antialias=False, smooth=None,
+            smooth_box=None, return_jitter=False):
     """The loop behind the command, on decoded frames.
 
     frames: without `track` a list of uint8 BGR arrays [H,W,3] of any sizes, taken `bs` at a time; with `track` a list of sequences (each
@@ -219,7 +311,15 @@ def predict(eng, frames, boxes=None, ratio=0.8, stage=2, bs=32, track=False, kee
     boxes: one (x0, y0, x1, y1) or None per image (with `track` per sequence: the box of its frame 0); None: whole frames.
     -> a list of records (the JSON fields; with `track` one list per sequence), each with 'crop' (uint8 [256,256,3]) when keep_crops and
     'stage' (the stage's meshes, projections and joint uv as numpy arrays) when keep_stage.  antialias: anti-aliased crops where a crop
-    shrinks its frame; every record then has 'antialiased'."""
+    shrinks its frame; every record then has 'antialiased'.
+    smooth / smooth_box (with `track`; True or a dict of utils.smooth.OneEuro's parameters): Tracker's.  With smooth a record's left, right
+    and offset are filtered, 'raw' holds the unfiltered ones, and keep_stage adds 'stage_smoothed' (PredictionSmoother.crop_stage);
+    return_jitter -> (records, [sequence_jitter per sequence])."""
+    if (smooth or smooth_box) and not track:
+        raise ValueError('predict: smooth and smooth_box need track=True')
+    if return_jitter and not smooth:
+        raise ValueError('predict: return_jitter needs smooth')
+    jit = [None] * len(frames)
     if track:
         groups = lockstep_groups([list(s) for s in frames], bs)
         out = [[] for _ in frames]
@@ -230,8 +330,9 @@ def predict(eng, frames, boxes=None, ratio=0.8, stage=2, bs=32, track=False, kee
     def box_of(e, h, w):
         return [float(v) for v in boxes[e[0]]] if boxes is not None and boxes[e[0]] is not None else [0.0, 0.0, w - 1.0, h - 1.0]
     for steps in groups:
-        for st, recs, crops, outs in _walk(eng, steps, lambda k: [f for _, f in steps[k]], lambda e: str(e[0]), box_of, ratio, stage, track, keep_stage,
-                                            antialias):
+        tr = None
+        for st, recs, crops, outs, tr in _walk(eng, steps, lambda k: [f for _, f in steps[k]], lambda e: str(e[0]), box_of, ratio, stage, track,
+                                                keep_stage, antialias, smooth, smooth_box):
             ch = crops.cpu().numpy() if keep_crops else None
             for j, ((i, _), r) in enumerate(zip(st, recs)):
                 if keep_crops:
@@ -240,14 +341,18 @@ def predict(eng, frames, boxes=None, ratio=0.8, stage=2, bs=32, track=False, kee
                     out[i].append(r)
                 else:
                     out[i] = r
-    return out
+        if return_jitter and tr is not None:
+            for i, j in sequence_jitter(tr, steps).items():
+                jit[i] = j
+    return (out, jit) if return_jitter else out
 
 
 def run(eng, sequences, out_dir, boxes=None, ratio=0.8, stage=2, bs=32, track=False, workers=8, pictures=False, joints=False, obj=False,
-        renderer=None, faces=None, antialias=False):
+        renderer=None, faces=None, antialias=False, smooth=None, smooth_box=None, jitter_out=None):
     """files -> files.  sequences: [[paths]] (one list without `track`).  -> (images, seconds, seconds of them spent waiting for decoded
     frames).  Two steps are decoded ahead of the GPU by at most 16 threads; the files are written by 8 more.  With `track`, more than `bs`
-    sequences walk `bs` at a time, so that no batch holds more than `bs` images."""
+    sequences walk `bs` at a time, so that no batch holds more than `bs` images.  smooth / smooth_box: Tracker's; with smooth the pictures
+    and OBJs show the filtered prediction, every sequence gets a jitter.json, and a list given as jitter_out receives their contents."""
     from concurrent.futures import ThreadPoolExecutor
 
     from ..utils import vis_utils as V
@@ -278,15 +383,17 @@ def run(eng, sequences, out_dir, boxes=None, ratio=0.8, stage=2, bs=32, track=Fa
                 frames = [f.result() for f in ahead.pop(k)]
                 wait[0] += time.perf_counter() - w0
                 return frames
-            for st, recs, crops, outs in _walk(eng, steps, load, lambda e: e[1], lambda e, h, w: box_for(boxes, e[1], h, w), ratio, stage, track, False,
-                                            antialias):
+            tr = None
+            for st, recs, crops, outs, tr in _walk(eng, steps, load, lambda e: e[1], lambda e, h, w: box_for(boxes, e[1], h, w), ratio, stage, track,
+                                                    False, antialias, smooth, smooth_box):
+                shown = tr.drawn(outs) if pictures or obj else None
                 if pictures:
-                    over = V.overlay_predictions(outs[stage], crops, renderer)
+                    over = V.overlay_predictions(shown, crops, renderer)
                     if joints:
-                        over = V.draw_joints(over, outs[stage]['pd_joint_uv_left'], outs[stage]['pd_joint_uv_right'])
+                        over = V.draw_joints(over, shown['pd_joint_uv_left'], shown['pd_joint_uv_right'])
                     ch, oh = crops.cpu().numpy(), over.cpu().numpy()
                 if obj:
-                    _, _, vl, vr = V.prediction_camera(outs[stage])
+                    _, _, vl, vr = V.prediction_camera(shown)
                     vh = np.concatenate([vl.cpu().numpy(), vr.cpu().numpy()], 1)
                 for j, ((_, p), r) in enumerate(zip(st, recs)):
                     jobs.append(wr.submit(dump, target(p, '.json'), r))
@@ -295,6 +402,11 @@ def run(eng, sequences, out_dir, boxes=None, ratio=0.8, stage=2, bs=32, track=Fa
                     if obj:
                         jobs.append(wr.submit(write_obj, target(p, '.obj'), vh[j], faces))
                 done += len(st)
+            if smooth and tr is not None:
+                for i, j in sequence_jitter(tr, steps).items():
+                    jobs.append(wr.submit(dump, os.path.join(os.path.dirname(target(sequences[i][0], '.json')), 'jitter.json'), j))
+                    if jitter_out is not None:
+                        jitter_out.append(j)
         for j in jobs:
             j.result()
     return done, time.perf_counter() - t0, wait[0]
@@ -324,9 +436,22 @@ def main(argv=None):
     ap.add_argument('--joints', action='store_true', help='draw the predicted 2-D joints on the overlay')
     ap.add_argument('--obj', action='store_true', help='write <stem>.obj: both predicted hands in one frame')
     ap.add_argument('--antialias', action='store_true', help='anti-aliased crops where the crop shrinks the frame (hand boxes larger than 256 px)')
+    ap.add_argument('--smooth', action='store_true', help='with --track: One-Euro temporal smoothing of every prediction stream, in frame space; writes jitter.json')
+    ap.add_argument('--smooth_box', action='store_true', help='with --track: smooth the next tracked box before the next crop is made (changes the crops)')
+    ap.add_argument('--fps', type=float, default=None, help='the frame rate of the sequence (default 30)')
+    ap.add_argument('--min_cutoff', type=float, default=None, help='One-Euro: the cutoff at rest, Hz (default 1.0, the paper\'s; not tuned on real video)')
+    ap.add_argument('--beta', type=float, default=None, help='One-Euro: cutoff per speed, Hz per (mm/s or px/s) (default 0.007)')
+    ap.add_argument('--d_cutoff', type=float, default=None, help='One-Euro: the cutoff of the speed estimate, Hz (default 1.0)')
     opt = ap.parse_args(argv)
     if opt.bs < 1:
         ap.error('--bs must be at least 1')
+    params = {k: getattr(opt, k) for k in ('fps', 'min_cutoff', 'beta', 'd_cutoff') if getattr(opt, k) is not None}
+    if (opt.smooth or opt.smooth_box or params) and not opt.track:
+        ap.error('--smooth, --smooth_box, --fps, --min_cutoff, --beta and --d_cutoff need --track')
+    if params and not (opt.smooth or opt.smooth_box):
+        ap.error('--fps, --min_cutoff, --beta and --d_cutoff need --smooth or --smooth_box')
+    if any(v <= 0 for k, v in params.items() if k != 'beta') or params.get('beta', 0.0) < 0:
+        ap.error('--fps, --min_cutoff and --d_cutoff must be positive and --beta not negative')
     sequences = list_sequences(opt.input) if opt.track else [list_images(opt.input)]
     if not any(sequences):
         raise ValueError('predict: no image files (%s) in %s' % (' / '.join(EXTENSIONS), opt.input))
@@ -344,9 +469,13 @@ def main(argv=None):
         if opt.pictures:
             renderer = V.mano_two_hands_shaded_renderer(right_faces=mano['right'].get_faces(), dense_color=np.zeros((V.NV_HAND, 3)), img_size=SIZE,
                                                         device=eng.device)
+    jitters = []
     n, sec, wait = run(eng, sequences, opt.out, boxes, opt.ratio, opt.stage, opt.bs, opt.track, opt.workers, opt.pictures, opt.joints, opt.obj,
-                       renderer, faces, opt.antialias)
+                       renderer, faces, opt.antialias, (params or True) if opt.smooth else None, (params or True) if opt.smooth_box else None, jitters)
     print('waited %.2f s of them for decoded frames' % wait)
+    if opt.smooth:
+        mm, px = jitter_summary(jitters)
+        print('jitter, raw -> smoothed: %.4g -> %.4g mm/frame^2 (meshes, 3-D joints, offset), %.4g -> %.4g px/frame^2 (2-D joints)' % (mm + px))
     print('%d images in %.1f s: %.0f images/s' % (n, sec, n / max(sec, 1e-9)))
     return n
 

@@ -11,6 +11,8 @@ tests/helpers/crop_ref.py.
                               antialias=True: where M shrinks the frame, Pillow's resize(BILINEAR, box) instead (no aliasing)
   to_frame_pixels             normalised crop uv [B,N,2] -> frame pixels
   frame_camera                (s, t) of uv = s xy + t -> (scale_px, trans_px) with frame pixel = scale_px xy + trans_px
+  from_frame_pixels           frame pixels -> normalised crop uv: the float64 inverse of to_frame_pixels
+  crop_camera                 (scale_px, trans_px) -> (s, tx, ty) of a crop: the float64 inverse of frame_camera
 """
 import ctypes
 
@@ -206,3 +208,19 @@ def frame_camera(proj, M, size=256):
     scale = p[:, 0] * float(size) / 2.0 / M[:, 0]
     trans = ((p[:, 1:3] + 1.0) * float(size) / 2.0 - M[:, (2, 5)]) / M[:, 0:1]
     return scale.float(), trans.float()
+
+
+def from_frame_pixels(px, M, size=256):
+    """frame pixel positions [B,N,2] -> normalised crop coordinates of the crop M, float64 [B,N,2]: (px M[:, 0] + M[:, (2, 5)]) 2 / size - 1,
+    the inverse of to_frame_pixels in float64, NOT rounded to float32 (the caller rounds once)"""
+    M = M.reshape(-1, 6)
+    return (px.double() * M[:, None, 0:1] + M[:, None, (2, 5)]) * 2.0 / float(size) - 1.0
+
+
+def crop_camera(scale_px, trans_px, M, size=256):
+    """(scale_px [B], trans_px [B,2]) with frame pixel = scale_px xy + trans_px -> proj float64 [B,3] = (s, tx, ty) with uv = s xy + t in the
+    crop M: the inverse of frame_camera in float64, NOT rounded to float32 (the caller rounds once)"""
+    M = M.reshape(-1, 6)
+    s = scale_px.double() * M[:, 0] * 2.0 / float(size)
+    t = (trans_px.double() * M[:, 0:1] + M[:, (2, 5)]) * 2.0 / float(size) - 1.0
+    return torch.cat((s[:, None], t), 1)

@@ -29,7 +29,7 @@ extern "C" {
 #define DIR_E_LAUNCH (-2)   /* hipLaunchKernel / HIP runtime error          */
 #define DIR_E_NODEVICE (-3) /* no gfx950 device visible                     */
 
-#define DIR_ABI_VERSION 46
+#define DIR_ABI_VERSION 47
 
 int dir_abi_version(void);
 const char* dir_last_error(void);
@@ -1230,6 +1230,45 @@ int dir_crop_frames(const uint8_t* frames, long long frames_bytes, const dir_fra
                     int B, int size, uint8_t* out, int32_t* status, void* stream);
 int dir_crop_frames_area(const uint8_t* frames, long long frames_bytes, const dir_frame_desc* descs, const double* M, const int32_t* valid,
                          int B, int size, uint8_t* out, int32_t* status, int32_t* area, void* stream);
+
+/* ---- temporal smoothing of tracked predictions: the One-Euro filter with a jitter measure (csrc/smooth.hip) ----
+ * Casiez, Roussel, Vogel, "1 Euro Filter", CHI 2012: an exponential filter whose cutoff rises with the filtered speed.  The reference has
+ * no temporal code: the rule below is this project's own, restated in float64 numpy by tests/helpers/one_euro_ref.py.  One launch per
+ * frame over every stream of every sequence, state updated in place, no atomics, no workspace, no host read; capturable in a graph.
+ *   x        float32 [B,F]: one row per sequence, this frame's values.  A row is a list of S <= DIR_ONE_EURO_MAX_SEGMENTS segments, each
+ *            n_points points of dims (1..4) components, point-major; F = sum n_points dims <= DIR_ONE_EURO_MAX_VALUES.  A POINT gets one
+ *            cutoff.  `segments` is a HOST array, passed to the kernel by value.
+ *   valid    int32 [B] or NULL;  y float32 [B,F], may be x;  updated int32 [B]
+ *   state    B rows of dir_one_euro_state_bytes(F, S, offsets) bytes each, zeroed by the caller before the first frame, 8-byte aligned.
+ *            offsets[9] (or NULL) receives the byte offsets inside a row of: jitter (double [S,2]: raw, filtered), y1, y2 (the last two
+ *            outputs), x1, x2 (the last two raw inputs), dxhat (float32 [F] each), age, run, count (int32).  The state is row-major per
+ *            sequence: the first B rows of a larger state are the state of a smaller batch (sequences end from the tail).  age: 0 =
+ *            never initialised, else frames since the last update (saturating); run: consecutive updates.
+ *            dir_one_euro_state_bytes is a pure host function; -1 for F or S outside their limits.
+ * Per row:
+ *   1. usable iff valid is NULL or valid[b] != 0, and all F inputs are finite.
+ *   2. not usable: y = x bit for bit; age += 1 if age > 0; run = 0; updated = 0; nothing else changes.
+ *   3. usable with age == 0 or age > max_gap: y = x, dxhat = 0, age = 1, run = 1, updated = 2 (initialised).
+ *   4. otherwise: dt = age / fps;  alpha(fc) = 1 / (1 + 1 / (2 pi fc dt));  per component dx = (x - y1) / dt, dxhat += alpha(d_cutoff)
+ *      (dx - dxhat);  per point v = speed_scale |dxhat|_2 over its components, fc = min_cutoff + beta v, y = y1 + alpha(fc) (x - y1): a
+ *      constant input comes out bit for bit.  Then age = 1, run += 1, updated = 1.  Float32 arithmetic, every operation rounded on its
+ *      own; dt, 2 pi dt and alpha(d_cutoff) are computed in double and rounded once.
+ *   5. jitter: when run >= 3 after the update, jitter[s] gains the sum over the segment's points of |x - 2 x1 + x2|_2 (raw) and of
+ *      |y - 2 y1 + y2|_2 (filtered), in double, and count gains 1.  Per-lane partials in point order, then a fixed tree: the same bits
+ *      from run to run.
+ *   6. x2 = x1, x1 = x, y2 = y1, y1 = y.
+ * A sequence gives the same bits in any batch slot of any batch size.
+ * A null pointer (valid aside), B outside 1..DIR_CROP_MAX_BATCH, S outside 1..DIR_ONE_EURO_MAX_SEGMENTS, dims outside 1..4, F over the
+ * limit, fps, min_cutoff or d_cutoff <= 0, beta < 0 or max_gap < 1 gives DIR_E_INVALID before any launch. */
+#define DIR_ONE_EURO_MAX_SEGMENTS 16
+#define DIR_ONE_EURO_MAX_VALUES 16384
+typedef struct dir_one_euro_segment {
+    int32_t n_points, dims;
+    float speed_scale;      /* the speed's unit: v = speed_scale |dxhat| (1000 for metres -> mm/s) */
+} dir_one_euro_segment;     /* 12 bytes */
+long long dir_one_euro_state_bytes(int F, int S, long long* offsets);
+int dir_one_euro_step(const float* x, const int32_t* valid, int B, const dir_one_euro_segment* segments, int S, double fps, double min_cutoff,
+                      double beta, double d_cutoff, int max_gap, void* state, float* y, int32_t* updated, void* stream);
 
 #ifdef __cplusplus
 }
