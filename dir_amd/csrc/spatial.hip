@@ -485,8 +485,9 @@ __global__ __launch_bounds__(256) void bone_proj_kernel(BoneArgs a) {
         const float ylo = fminf(ay, by) - d - 0.5f, yhi = fmaxf(ay, by) + d - 0.5f;
         const float xlo = fminf(ax, bx) - d - 0.5f, xhi = fmaxf(ax, bx) + d - 0.5f;
         const bool finite = (ax - ax == 0.f) && (ay - ay == 0.f) && (bx - bx == 0.f) && (by - by == 0.f);
-        // NaN / inf joints give a NaN or inf distance for every pixel -> mask all false -> empty box
-        if (!finite) { bb[0] = 1; bb[1] = 0; bb[2] = 1; bb[3] = 0; }
+        // NaN / inf joints give a NaN or inf distance for every pixel -> mask all false -> empty box; so does a bone of zero length
+        // (coincident joints: its unit direction is 0 / 0)
+        if (!finite || (ax == bx && ay == by)) { bb[0] = 1; bb[1] = 0; bb[2] = 1; bb[3] = 0; }
         else {
             const float fs = (float)(S - 1);
             bb[0] = (int)fminf(fmaxf(floorf(ylo), 0.f), fs + 1.f); bb[1] = (int)fmaxf(fminf(ceilf(yhi), fs), -1.f);

@@ -311,12 +311,12 @@ def test_bone_bbox_is_conservative_and_sparse_conv_is_bit_identical(golden):
             assert torch.equal(dense, sparse), 'sparse-K conv differs from dense (S=%d, %s)' % (S, tdt)
 
 
-@pytest.mark.parametrize('S,dist,B', [(16, 1, 3), (32, 2, 2), (32, 2, 5)])
-def test_bone_fusion_factorised_vs_oracle(golden, S, dist, B):
-    """dir_bone_fusion_forward (bone_proj + fusion conv + BN + ReLU as a K = 720 reduction) against the oracle's
-    bone_proj -> conv2d 3x3 -> scale/shift -> ReLU in float64, against the reference's own bone map (g5_bone golden) pushed
-    through the same float64 conv, and against the materialised GPU path (dir_bone_proj_forward + dir_conv2d_forward).
-    Tolerance: bf16 operands (weights, G, pixel weights: 2^-9 each) and a bf16 output -> 1.5e-2 of the output scale."""
+_FUSION_CASE = {}     # (S, B) -> inputs and the float64 reference, computed once and shared by the two storage types
+
+
+def _fusion_case(golden, S, dist, B):
+    if (S, B) in _FUSION_CASE:
+        return _FUSION_CASE[(S, B)]
     g = golden('g5_bone')
     uv0 = g['S%d.uv' % S]                                                        # [2,21,2] from the reference fixture
     rng = np.random.default_rng(7 + S + B)
@@ -325,7 +325,7 @@ def test_bone_fusion_factorised_vs_oracle(golden, S, dist, B):
     uv_r = uv_l.copy(); uv_r[..., 0] *= -0.9
     emb = synth.synth_input('bonefuse.emb%d' % S, (B, 42, 64), SEED)
     w = (rng.standard_normal((256, 2560, 3, 3)) * 0.02).astype(np.float32)
-    w = torch.from_numpy(w).to(torch.bfloat16).float().numpy()                   # the bf16 mode's weights
+    w = torch.from_numpy(w).to(torch.bfloat16).float().numpy()                   # the bf16 mode's weights (8 significant bits: f16 values too)
     scale = (1 + 0.1 * rng.standard_normal(256)).astype(np.float32)
     shift = (0.1 * rng.standard_normal(256)).astype(np.float32)
     # oracle, float64
@@ -334,33 +334,58 @@ def test_bone_fusion_factorised_vs_oracle(golden, S, dist, B):
         assert np.array_equal((img[:, :1280] != 0).reshape(2, 20, 64, S, S).any(2), (g['S%d.y' % S] != 0).reshape(2, 20, 64, S, S).any(2))
     ref = N.conv2d(img.astype(np.float64), w.astype(np.float64), None, 1, 1)
     ref = np.maximum(ref * scale[None, :, None, None] + shift[None, :, None, None], 0)
+    ref.setflags(write=False)
+    _FUSION_CASE[(S, B)] = (uv_l, uv_r, emb, w, scale, shift, ref)
+    return _FUSION_CASE[(S, B)]
+
+
+@pytest.mark.parametrize('storage', ['bf16', 'f16'])
+@pytest.mark.parametrize('S,dist,B', [(16, 1, 3), (32, 2, 2), (32, 2, 5)])
+def test_bone_fusion_factorised_vs_oracle(golden, S, dist, B, storage):
+    """dir_bone_fusion_forward (bone_proj + fusion conv + BN + ReLU as a K = 720 reduction) against the oracle's
+    bone_proj -> conv2d 3x3 -> scale/shift -> ReLU in float64, against the reference's own bone map (g5_bone golden) pushed
+    through the same float64 conv, and against the materialised GPU path (dir_bone_proj_forward + dir_conv2d_forward).
+    Tolerance: bf16 operands (weights, G, pixel weights: 2^-9 each) and a bf16 output -> 1.5e-2 of the output scale.
+    storage = f16 (exact_f32 = 2: bone_g_kernel<false, f16s_t> + bone_fuse_kernel<f16s_t>, float16 output and materialised path): the same
+    inputs, the same assertions, and an error against float64 no larger than the bf16 kernels' on those inputs."""
+    uv_l, uv_r, emb, w, scale, shift, ref = _fusion_case(golden, S, dist, B)
+    tdt, exact, sdt = (torch.bfloat16, 0, _capi.DT_BF16) if storage == 'bf16' else (torch.float16, 2, _capi.DT_F16)
     # GPU: factorised
     L = _capi.lib()
     dw = torch.from_numpy(w).cuda()
     wg = dw.reshape(256, 40, 64, 9).permute(3, 1, 2, 0).contiguous()
     dsc, dsh = dev(scale), dev(shift)
-    P = _capi.BoneFusionParams(wg.data_ptr(), dsc.data_ptr(), dsh.data_ptr())
     duv, duvr, demb = dev(uv_l), dev(uv_r), dev(emb)
-    scratch = torch.empty(L.dir_bone_fusion_scratch_bytes(B), device='cuda', dtype=torch.uint8)
-    y = torch.full((B, S, S, 320), 7.0, device='cuda', dtype=torch.bfloat16)      # written into channels [32, 288)
-    _capi.check(L.dir_bone_fusion_prepare(P, _capi.ptr(demb), _capi.ptr(scratch), B, _capi.stream_ptr()), 'bone_fusion_prepare')
-    _capi.check(L.dir_bone_fusion_forward(P, _capi.ptr(duv), _capi.ptr(duvr), _capi.ptr(scratch), _capi.ptr(y),
-                                          B, S, float(dist), 320, 32, 1, _capi.stream_ptr()), 'bone_fusion')
-    torch.cuda.synchronize()
-    got = y[..., 32:288].float().cpu().numpy().transpose(0, 3, 1, 2)
+
+    def factorised(exact, tdt):
+        P = _capi.BoneFusionParams(wg.data_ptr(), dsc.data_ptr(), dsh.data_ptr(), exact)
+        scratch = torch.empty(L.dir_bone_fusion_scratch_bytes(B), device='cuda', dtype=torch.uint8)
+        y = torch.full((B, S, S, 320), 7.0, device='cuda', dtype=tdt)      # written into channels [32, 288)
+        _capi.check(L.dir_bone_fusion_prepare(P, _capi.ptr(demb), _capi.ptr(scratch), B, _capi.stream_ptr()), 'bone_fusion_prepare')
+        _capi.check(L.dir_bone_fusion_forward(P, _capi.ptr(duv), _capi.ptr(duvr), _capi.ptr(scratch), _capi.ptr(y),
+                                              B, S, float(dist), 320, 32, 1, _capi.stream_ptr()), 'bone_fusion')
+        torch.cuda.synchronize()
+        assert float(y[..., :32].float().min()) == 7.0 and float(y[..., 288:].float().max()) == 7.0     # slice untouched outside
+        return y[..., 32:288].float().cpu().numpy().transpose(0, 3, 1, 2)
+
+    got = factorised(exact, tdt)
     sc = np.abs(ref).max()
     assert maxabs(got, ref) <= 1.5e-2 * sc, (maxabs(got, ref), sc)
-    assert float(y[..., :32].float().min()) == 7.0 and float(y[..., 288:].float().max()) == 7.0     # slice untouched outside
-    # GPU: materialised bone map + implicit-GEMM conv (the fp32-mode path, here in bf16)
-    bone = torch.empty(B, S, S, 2560, device='cuda', dtype=torch.bfloat16)
+    # GPU: materialised bone map + implicit-GEMM conv (the fp32-mode path, here in the 16-bit storage type)
+    bone = torch.empty(B, S, S, 2560, device='cuda', dtype=tdt)
     _capi.check(L.dir_bone_proj_forward(_capi.ptr(duv), _capi.ptr(duvr), _capi.ptr(demb), _capi.ptr(bone), None, None, B, S,
-                                        float(dist), 1, _capi.stream_ptr()), 'bone_proj')
+                                        float(dist), sdt, _capi.stream_ptr()), 'bone_proj')
     from dir_amd import functional as Fn
-    wp = dw.permute(0, 2, 3, 1).contiguous().to(torch.bfloat16)
+    wp = dw.permute(0, 2, 3, 1).contiguous().to(tdt)
     y2 = Fn.conv2d_nhwc(bone, wp, 1, 1, scale=dsc, shift=dsh, relu=True).float().cpu().numpy().transpose(0, 3, 1, 2)
     assert maxabs(got, y2) <= 1.5e-2 * sc
-    # and the factorised result is at least as close to the float64 value as the materialised bf16 path
+    # and the factorised result is at least as close to the float64 value as the materialised 16-bit path
     assert maxabs(got, ref) <= 1.25 * maxabs(y2, ref) + 1e-3 * sc
+    if storage == 'f16':
+        e_bf16 = maxabs(factorised(0, torch.bfloat16), ref)
+        print('factorised fusion S=%d B=%d vs float64: f16 %.2e, bf16 %.2e of the output scale' % (S, B, maxabs(got, ref) / sc, e_bf16 / sc))
+        assert maxabs(got, ref) <= e_bf16, (maxabs(got, ref), e_bf16)
+
 
 @pytest.mark.parametrize('S,dist,B', [(16, 1, 2), (32, 2, 2), (32, 2, 5)])
 def test_bone_fusion_exact_fp32_vs_oracle(golden, S, dist, B):
