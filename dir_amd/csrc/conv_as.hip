@@ -19,6 +19,23 @@
 // K order and k-slot assignment are conv.hip's (64-channel slab outer, taps inner; MFMA ks of a slab multiplies channels 8 ks .. + 8 in lanes 0-31 and
 // 32 + 8 ks .. + 8 in lanes 32-63; taps outside the image multiply zeros, as the tiled kernels' hardware-zeroed halo does): the same fp32 chains, so
 // the outputs are bit-identical and the engine's autotune may pick this kernel per layer (DIR_CONV_VARIANT 25 .. 28).
+//
+// CHAINED MODE (template parameter CH, dir_conv2d_as_chain_forward): the 3x3 on the 32x32 map and the 1x1 that alone reads it as one launch --
+//   models/dir.py:474-476     conv_final: 3x3 256 -> 256 + BN + ReLU, then 1x1 256 -> 256 + bias                                   (CH = 1)
+//   models/dir.py:425-433     seg / dense heads: 3x3 + BN + ReLU, then 1x1 -> 3 each; merged: 256 -> 256, then 256 -> 6 as fp32     (CH = 2)
+// In the (A, PB) = (2, 4) shape a workgroup owns 128 pixels x ALL 256 output channels, so when the 3x3's reduction ends one CU holds everything
+// the 1x1 needs.  After the K loop:
+//   1. the 1x1's whole weight stream (K = 256 = 4 steps: exactly the ring wr[4][4][A]) is loaded, in flight across steps 2 - 3;
+//   2. barrier (the patch is dead); epilogue 1 IN REGISTERS: fmaf(acc, scale, shift), rounded to the storage kind and ReLU'd with the helpers the
+//      unchained path stores with (f16: saturating), 8 bytes per lane into LDS at pixel * (2 * 256 + 16) + 2 * channel -- the K3 = false patch
+//      layout, so the second reduction reads its B operand with the K loop's 1x1 addressing.  No fp32 stage, no global store;
+//   3. barrier; the second GEMM from zeroed accumulators, same slab order and k-slots (the same fp32 chains as the separate launch).  CH = 1:
+//      A = 2, all four waves, 128 MFMAs per wave (the 3x3: 1152).  CH = 2: the <= 8 real channels are one 32-channel block (zero rows above
+//      them, host-padded); wave w multiplies it with pixel block w: 16 MFMAs;
+//   4. epilogue 2.  CH = 1: the unchained epilogue on the 1x1's scale / shift (barrier, fp32 stage over the tile, 16-byte stores into a channel
+//      slice).  CH = 2: lane (pixel n, half h) holds channels 4 h .. + 3 in d[0 .. 3]: fmaf, then 8-byte fp32 NHWC stores of the real channels.
+// LDS: 107 KB patch, then the 67.6 KB tile over it, then (CH = 1) the 133 KB stage over that.  The 33.5 MB map between the two layers (B = 64)
+// is neither written nor read, and one launch and its ramp go away per pair.
 #include "conv_common.h"
 
 namespace dir {
@@ -43,6 +60,9 @@ struct AsArgs {
     unsigned mg_q, sh_q, mg_pw, sh_pw; // magic divisors (conv_common.h: magic_u31) of q + 1 and PW
     unsigned x_bytes;
     long long* stamps;                 // DIR_STAMPS=conv_as (tuning aid, else NULL): phase times of workgroup 0
+    // chained mode (CH != 0) only: the 1x1 that follows.  y / out_cs / out_co are then ITS output (the 3x3's map is never stored), scale / shift / relu the 3x3's
+    const uint4* w2; const float* scale2; const float* shift2;
+    int cout2, relu2;
 };
 
 // A: 32-channel blocks per wave (workgroup = 128 A output channels); PB: 32-pixel blocks per workgroup; K3: 3x3 / pad 1 (else 1x1);
@@ -50,8 +70,10 @@ struct AsArgs {
 // CHK: the patch does not fit LDS as a whole (the attention convolution: 100 positions x 2048 channels = 411 KB): it is brought in KC channels at a
 // time into a ring of TWO buffers -- chunk c + 1's DMA is issued (from source offsets kept in registers: one add per instruction) while chunk c is
 // multiplied; one wait + barrier per chunk.  The K order is unchanged (slab outer, taps inner: a chunk is KC / 64 whole slabs).
-template <typename H, int A, int PB, bool K3, int NSTG, bool CHK = false>
+// CH: chained mode (top of the file).  0: none; 1: + 1x1 256 -> 256, 16-bit out; 2: + 1x1 256 -> cout2 <= 8, fp32 out.  Built for (2, 4, K3, 4, !CHK) only.
+template <typename H, int A, int PB, bool K3, int NSTG, bool CHK = false, int CH = 0>
 __global__ __launch_bounds__(AS_THR, (A * PB <= 4 && NSTG <= 3 && !CHK) ? 2 : 1) void conv_as_kernel(AsArgs a) {
+    static_assert(CH == 0 || (A == 2 && PB == 4 && K3 && NSTG == 4 && !CHK), "the chained mode is built on the (2, 4) 3x3 shape only");
     convk::half_kernel_init<H>();
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NWG = 128 * A, TPX = 32 * PB, NTAP = K3 ? 9 : 1;
@@ -153,9 +175,9 @@ __global__ __launch_bounds__(AS_THR, (A * PB <= 4 && NSTG <= 3 && !CHK) ? 2 : 1)
     //      stages lane n's results at that pixel.  pix[pb]: pixel index in the tile (row-major); posb[pb]: LDS address of its tap (0, 0), slab 0,
     //      this lane half's chunk (4 h) of k-step 0.
     int pix[PB], posb[PB];
+    const bool g1 = ((l32 >= 4) & (l32 < 12)) | ((l32 >= 16) & (l32 < 20)) | (l32 >= 28);
+    const int rk = g1 ? (l32 < 12 ? l32 - 4 : l32 < 20 ? l32 - 8 : l32 - 16) : (l32 < 4 ? l32 : l32 < 16 ? l32 - 8 : l32 - 12);      // rank inside the group
     {
-        const bool g1 = ((l32 >= 4) & (l32 < 12)) | ((l32 >= 16) & (l32 < 20)) | (l32 >= 28);
-        const int rk = g1 ? (l32 < 12 ? l32 - 4 : l32 < 20 ? l32 - 8 : l32 - 16) : (l32 < 4 ? l32 : l32 < 16 ? l32 - 8 : l32 - 12);      // rank inside the group
 #pragma unroll
         for (int pb = 0; pb < PB; ++pb) {
             const int seg = 2 * pb + (g1 ? 1 : 0);
@@ -246,7 +268,94 @@ __global__ __launch_bounds__(AS_THR, (A * PB <= 4 && NSTG <= 3 && !CHK) ? 2 : 1)
 
     // ---- epilogue (conv.hip's arithmetic): fmaf(acc, scale, shift) as fp32 through LDS, then per 16-byte output chunk + residual, round, ReLU
     stamp();                           // K loop done (this wave)
-    __syncthreads();                   // every wave is done with the patch
+    if constexpr (CH != 0) {
+        // ---- chained 1x1 (top of the file).  Its whole weight stream -- K = 256 = 4 steps -- fits the ring: in flight across epilogue 1
+        {
+            const uint4* p2 = a.w2 + (CH == 1 ? (long long)wave * 4 * (4 * A * 64) : 0) + lane;      // CH == 2: every wave reads wave 0's share of an A = 1 stream
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+                    for (int cb = 0; cb < (CH == 1 ? A : 1); ++cb) wr[s][ks][cb] = p2[CH == 1 ? ((s * 4 + ks) * A + cb) * 64 : (s * 4 + ks) * 64];
+        }
+        __syncthreads();               // every wave is done with the patch
+        // epilogue 1, in registers: the 3x3's map rounded to the storage kind exactly as the unchained path stores it, as the 1x1's B operand in LDS
+        constexpr int TP = 2 * NWG + 16;          // the K3 = false patch layout at 256 channels: pixel p from p * TP, channel c at + 2 c
+        const bool relu1 = a.relu != 0;
+#pragma unroll
+        for (int cb = 0; cb < A; ++cb)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int cl = (wave * A + cb) * 32 + 8 * q + 4 * h;
+                float4 sc = make_float4(1.f, 1.f, 1.f, 1.f), sh = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (a.scale) sc = *reinterpret_cast<const float4*>(a.scale + cl);
+                if (a.shift) sh = *reinterpret_cast<const float4*>(a.shift + cl);
+#pragma unroll
+                for (int pb = 0; pb < PB; ++pb) {
+                    const float v0 = fmaf(acc[cb][pb][4 * q], sc.x, sh.x), v1 = fmaf(acc[cb][pb][4 * q + 1], sc.y, sh.y);
+                    const float v2 = fmaf(acc[cb][pb][4 * q + 2], sc.z, sh.z), v3 = fmaf(acc[cb][pb][4 * q + 3], sc.w, sh.w);
+                    *reinterpret_cast<uint2*>(smem + pix[pb] * TP + 2 * cl) =
+                        relu1 ? make_uint2(Half<H>::pack2_relu(v0, v1), Half<H>::pack2_relu(v2, v3)) : make_uint2(Half<H>::pack2(v0, v1), Half<H>::pack2(v2, v3));
+                }
+            }
+        __syncthreads();               // the 128 x 256 tile is complete
+        if constexpr (CH == 1) {
+            // all four waves, A = 2: the K loop's arithmetic on 1x1 addressing (slab s at + 128 s, k-step ks at + 16 ks, lane half at + 64 h)
+#pragma unroll
+            for (int cb = 0; cb < A; ++cb)
+#pragma unroll
+                for (int pb = 0; pb < PB; ++pb)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) acc[cb][pb][r] = 0.f;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+#pragma unroll
+                for (int pb = 0; pb < PB; ++pb)
+#pragma unroll
+                    for (int ks = 0; ks < 4; ++ks) bv[s & 1][ks][pb] = *reinterpret_cast<const uint4*>(smem + pix[pb] * TP + 64 * h + 128 * s + 16 * ks);
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+                    for (int cb = 0; cb < A; ++cb)
+#pragma unroll
+                        for (int pb = 0; pb < PB; ++pb) acc[cb][pb] = Half<H>::mfma32(wr[s][ks][cb], bv[s & 1][ks][pb], acc[cb][pb]);
+            }
+            // epilogue 2 is the unchained epilogue below, on the 1x1's parameters
+            a.scale = a.scale2; a.shift = a.shift2; a.relu = a.relu2;
+            __syncthreads();           // every wave is done with the tile: the fp32 stage goes over it
+        } else {
+            // cout2 <= 8 real channels in ONE 32-channel block (zero rows above them): wave w multiplies it with pixel block w
+            const int p = 16 * (2 * wave + (g1 ? 1 : 0)) + rk;
+            f32x16 d;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) d[r] = 0.f;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks) bv[s & 1][ks][0] = *reinterpret_cast<const uint4*>(smem + p * TP + 64 * h + 128 * s + 16 * ks);
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks) d = Half<H>::mfma32(wr[s][ks][0], bv[s & 1][ks][0], d);
+            }
+            // lane (l32, h) holds channels 4 h .. 4 h + 3 of pixel p in d[0 .. 3]: fp32 NHWC, 8-byte stores (cout2, out_cs, out_co are even)
+            float* __restrict__ y = (float*)a.y + (((long long)img * a.H + trow) * a.W + p) * a.out_cs + a.out_co;
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const int n = 4 * h + 2 * e;
+                if (n < a.cout2) {
+                    const float s0 = a.scale2 ? a.scale2[n] : 1.f, s1 = a.scale2 ? a.scale2[n + 1] : 1.f;
+                    const float h0 = a.shift2 ? a.shift2[n] : 0.f, h1 = a.shift2 ? a.shift2[n + 1] : 0.f;
+                    float v0 = fmaf(d[2 * e], s0, h0), v1 = fmaf(d[2 * e + 1], s1, h1);
+                    if (a.relu2) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); }
+                    *reinterpret_cast<float2*>(y + n) = make_float2(v0, v1);
+                }
+            }
+            stamp();
+            return;
+        }
+    } else {
+        __syncthreads();               // every wave is done with the patch
+    }
     constexpr int SP = NWG * 4 + 16;   // bytes per staged pixel (the 16-byte skew spreads a wave's 32 pixels over the bank groups)
 #pragma unroll
     for (int cb = 0; cb < A; ++cb)
@@ -306,6 +415,22 @@ int launch_as(const AsArgs& a, size_t lds, hipStream_t s) {
     return check_launch("dir_conv2d_as_forward");
 }
 
+template <typename H, int CH>
+int launch_as_chain(const AsArgs& a, size_t lds, hipStream_t s) {
+    static bool attr_set = false;      // (per instantiation)
+    if (!attr_set) {
+        if (hipFuncSetAttribute((const void*)conv_as_kernel<H, 2, 4, true, 4, false, CH>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
+            set_error("dir_conv2d_as_chain_forward: cannot raise the dynamic LDS limit");
+            return DIR_E_LAUNCH;
+        }
+        attr_set = true;
+    }
+    AsArgs b = a;
+    b.stamps = stamps_begin("conv_as");
+    DIR_LAUNCH((conv_as_kernel<H, 2, 4, true, 4, false, CH>), dim3(a.ntile * a.nslice), dim3(AS_THR), lds, s, b);
+    stamps_end("conv_as", b.stamps, s);
+    return check_launch("dir_conv2d_as_chain_forward");
+}
 
 // How a layer's patch is held: whole (KC = Cin, one buffer) when it fits 160 KB beside nothing else, otherwise -- for the one shape built with a
 // chunk ring, (A, PB) = (4, 2) -- in the largest KC in {1024, 512, 256, 128} whose TWO buffers fit, whose steps per chunk are a multiple of the
@@ -357,6 +482,32 @@ extern "C" int dir_conv2d_as_supported(const dir_conv_desc* d, int blocks_per_wa
     return 1;
 }
 
+namespace dir {
+namespace {
+// the launch arguments of a supported layer (everything but the pointers)
+bool as_fill(const dir_conv_desc* d, int A, int PB, AsArgs& a, AsPlan& plan) {
+    const bool k3 = d->kh == 3;
+    a.B = d->B; a.H = d->H; a.W = d->W; a.logW = d->W == 8 ? 3 : d->W == 16 ? 4 : 5;
+    a.Cin = d->Cin; a.in_cs = d->in_cstride ? d->in_cstride : d->Cin; a.in_co = d->in_coff;
+    a.Cout = d->Cout; a.out_cs = d->out_cstride ? d->out_cstride : d->Cout; a.out_co = d->out_coff;
+    a.res_cs = d->res_cstride ? d->res_cstride : d->Cout; a.res_co = d->res_coff;
+    a.TR = 32 * PB / d->W;
+    a.tiles_per_img = d->H * d->W / (32 * PB); a.ntile = d->B * a.tiles_per_img; a.nslice = d->Cout / (128 * A);
+    a.nsteps = (k3 ? 9 : 1) * d->Cin / 64; a.relu = (d->flags & DIR_CONV_RELU) != 0;
+    a.xcd_map = a.ntile % 8 == 0;
+    if (!as_plan(d, A, PB, plan)) return false;
+    a.KC = plan.KC; a.nchunk = plan.nchunk; a.csteps = plan.csteps; a.chunk_bytes = plan.chunk_bytes; a.ninstr = plan.ninstr;
+    a.q = a.KC / 8; a.PW = k3 ? d->W + 2 : d->W; a.NP = (k3 ? a.TR + 2 : a.TR) * a.PW;
+    convk::magic_u31((unsigned)(a.q + 1), &a.mg_q, &a.sh_q);
+    convk::magic_u31((unsigned)a.PW, &a.mg_pw, &a.sh_pw);
+    a.x_bytes = (unsigned)((long long)d->B * d->H * d->W * a.in_cs * 2);
+    a.stamps = nullptr;
+    a.w2 = nullptr; a.scale2 = nullptr; a.shift2 = nullptr; a.cout2 = 0; a.relu2 = 0;
+    return true;
+}
+}  // namespace
+}  // namespace dir
+
 extern "C" int dir_conv2d_as_forward(const dir_conv_desc* d, const void* x, const void* w_as, const float* scale, const float* shift,
                                      const void* residual, void* y, int blocks_per_wave, int pixel_blocks, void* stream) {
     using namespace dir;
@@ -367,22 +518,8 @@ extern "C" int dir_conv2d_as_forward(const dir_conv_desc* d, const void* x, cons
     const bool k3 = d->kh == 3, f16 = d->in_dtype == DIR_DT_F16;
     AsArgs a;
     a.x = x; a.w = (const uint4*)w_as; a.scale = scale; a.shift = shift; a.res = residual; a.y = y;
-    a.B = d->B; a.H = d->H; a.W = d->W; a.logW = d->W == 8 ? 3 : d->W == 16 ? 4 : 5;
-    a.Cin = d->Cin; a.in_cs = d->in_cstride ? d->in_cstride : d->Cin; a.in_co = d->in_coff;
-    a.Cout = d->Cout; a.out_cs = d->out_cstride ? d->out_cstride : d->Cout; a.out_co = d->out_coff;
-    a.res_cs = d->res_cstride ? d->res_cstride : d->Cout; a.res_co = d->res_coff;
-    a.TR = 32 * PB / d->W;
-    a.tiles_per_img = d->H * d->W / (32 * PB); a.ntile = d->B * a.tiles_per_img; a.nslice = d->Cout / (128 * A);
-    a.nsteps = (k3 ? 9 : 1) * d->Cin / 64; a.relu = (d->flags & DIR_CONV_RELU) != 0;
-    a.xcd_map = a.ntile % 8 == 0;
     AsPlan plan;
-    DIR_REQUIRE(as_plan(d, A, PB, plan), "dir_conv2d_as_forward: no LDS plan for this layer");
-    a.KC = plan.KC; a.nchunk = plan.nchunk; a.csteps = plan.csteps; a.chunk_bytes = plan.chunk_bytes; a.ninstr = plan.ninstr;
-    a.q = a.KC / 8; a.PW = k3 ? d->W + 2 : d->W; a.NP = (k3 ? a.TR + 2 : a.TR) * a.PW;
-    convk::magic_u31((unsigned)(a.q + 1), &a.mg_q, &a.sh_q);
-    convk::magic_u31((unsigned)a.PW, &a.mg_pw, &a.sh_pw);
-    a.x_bytes = (unsigned)((long long)d->B * d->H * d->W * a.in_cs * 2);
-    a.stamps = nullptr;
+    DIR_REQUIRE(as_fill(d, A, PB, a, plan), "dir_conv2d_as_forward: no LDS plan for this layer");
     const size_t lds = plan.lds;
     hipStream_t s = (hipStream_t)stream;
     if (plan.chunked) {                // (A, PB) = (4, 2) on a ring of two patch chunks, weight ring of 4 steps
@@ -402,4 +539,46 @@ extern "C" int dir_conv2d_as_forward(const dir_conv_desc* d, const void* x, cons
 #undef DIR_AS
 #undef DIR_AS3
     DIR_REQUIRE(false, "dir_conv2d_as_forward: unsupported (A, PB) = (%d, %d)", A, PB);
+}
+
+extern "C" int dir_conv2d_as_chain_supported(const dir_conv_desc* d, int cout2, int out2_dtype) {
+    if (!d) return 0;
+    dir_conv_desc t = *d;              // the 3x3's own map is never stored: its output slice and residual fields do not matter
+    t.out_cstride = 0; t.out_coff = 0; t.res_cstride = 0; t.res_coff = 0; t.Ho = 0; t.Wo = 0;
+    if (d->Ho && (d->Ho != d->H || d->Wo != d->W)) return 0;
+    if (!(d->kh == 3 && d->kw == 3 && d->pad == 1 && d->W == 32 && d->Cout == 256)) return 0;
+    if (!dir_conv2d_as_supported(&t, 2, 4)) return 0;                                // 16-bit storage, stride 1, H W % 128 == 0, Cin % 64 == 0, the patch fits
+    if (out2_dtype == d->in_dtype) return cout2 == 256;
+    if (out2_dtype == DIR_DT_F32) return cout2 >= 2 && cout2 <= 8 && cout2 % 2 == 0;
+    return 0;
+}
+
+extern "C" int dir_conv2d_as_chain_forward(const dir_conv_desc* d, const void* x, const void* w_as, const float* scale, const float* shift,
+                                           const void* w2_as, const float* scale2, const float* shift2, int cout2, int relu2,
+                                           void* y, int out_cstride, int out_coff, int out_dtype, void* stream) {
+    using namespace dir;
+    DIR_REQUIRE(d && x && w_as && w2_as && y, "dir_conv2d_as_chain_forward: null pointer");
+    DIR_REQUIRE(dir_conv2d_as_chain_supported(d, cout2, out_dtype), "dir_conv2d_as_chain_forward: pair not supported (16-bit storage, 3x3 pad 1 stride 1 -> 256 channels, "
+                "W = 32, H W %% 128 == 0, Cin %% 64 == 0, patch <= 160 KB; then 1x1 -> 256 in the storage kind, or -> 2 | 4 | 6 | 8 channels as fp32)");
+    const bool f32out = out_dtype == DIR_DT_F32;
+    const int out_cs = out_cstride ? out_cstride : cout2;
+    DIR_REQUIRE(out_coff >= 0 && out_cs >= out_coff + cout2 && out_cs % (f32out ? 2 : 8) == 0 && out_coff % (f32out ? 2 : 8) == 0,
+                "dir_conv2d_as_chain_forward: bad output slice (stride %d, offset %d, %d channels)", out_cs, out_coff, cout2);
+    dir_conv_desc t = *d;
+    t.out_cstride = 0; t.out_coff = 0; t.res_cstride = 0; t.res_coff = 0; t.Ho = 0; t.Wo = 0;
+    AsArgs a;
+    a.x = x; a.w = (const uint4*)w_as; a.scale = scale; a.shift = shift; a.res = nullptr; a.y = y;
+    AsPlan plan;
+    DIR_REQUIRE(as_fill(&t, 2, 4, a, plan) && !plan.chunked, "dir_conv2d_as_chain_forward: no LDS plan for this layer");
+    a.out_cs = out_cs; a.out_co = out_coff;
+    a.w2 = (const uint4*)w2_as; a.scale2 = scale2; a.shift2 = shift2; a.cout2 = cout2; a.relu2 = relu2 != 0;
+    // LDS: the patch, then the 128 x (2 * 256 + 16)-byte tile, then (16-bit out) the fp32 stage -- each laid over the one before
+    size_t lds = (size_t)plan.chunk_bytes;
+    const size_t tile = 128 * (2 * 256 + 16), stage = 128 * (256 * 4 + 16);
+    if (lds < tile) lds = tile;
+    if (!f32out && lds < stage) lds = stage;
+    hipStream_t s = (hipStream_t)stream;
+    const bool f16 = d->in_dtype == DIR_DT_F16;
+    if (f32out) return f16 ? launch_as_chain<convk::f16s_t, 2>(a, lds, s) : launch_as_chain<convk::bf16_t, 2>(a, lds, s);
+    return f16 ? launch_as_chain<convk::f16s_t, 1>(a, lds, s) : launch_as_chain<convk::bf16_t, 1>(a, lds, s);
 }

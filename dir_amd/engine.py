@@ -1002,6 +1002,61 @@ class ResidualOp(object):
         return self.c3(self.c2(self.c1(x)), out=out, out_coff=out_coff, residual=res)
 
 
+class ConvChainOp(object):
+    """a 3x3 ConvOp on the 32x32 map and the 1x1 ConvOp that is its ONLY reader as one launch (conv_as.hip's chained mode,
+    dir_conv2d_as_chain_forward): models/dir.py:474-476 conv_final.0 -> conv_final.3 and models/dir.py:425-433 the merged seg | dense 3x3 -> their
+    1x1s.  The 3x3's map never reaches memory; bit-identical to the two launches.  16-bit storage modes only: everything else (and
+    DIR_HEAD_CHAIN=0) runs c1(c3(x)) as before.  For the tuning tables the pair stays TWO layers: the launch's profile record carries
+    op = the 3x3 and covers = (the 1x1,), and DirEngine expands it (a chained 3x3's variant code is a no-op, the covered row's is carried)."""
+
+    head_chain = os.environ.get('DIR_HEAD_CHAIN', '1') != '0'      # the A/B and test handle, as ResidualOp.res_chain
+
+    def __init__(self, c3, c1):
+        self.c3, self.c1 = c3, c1
+        self.cout, self.cin, self.kh, self.kw, self.stride = c3.cout, c3.cin, c3.kh, c3.kw, c3.stride      # what autotune_energy reads from a captured op
+        self.variant = c3.variant                              # (the 3x3's row)
+        self.w = None
+        f32_out = c1.out_dtype == F32
+        if (c3.dtype in HALF and c1.dtype == c3.dtype and c3.arith is None and c3.pre_scale is None and c1.pre_scale is None and (c1.flags & ~CONV_RELU) == 0
+                and (c1.kh, c1.kw, c1.stride, c1.pad, c1.cin) == (1, 1, 1, 0, c3.cout) and (f32_out or c1.out_dtype == c3.dtype)
+                and _capi.lib().dir_conv2d_as_chain_supported(self._desc(1, 32, 32, c3.cin), c1.cout, _dt(c1.out_dtype))):
+            # both weight streams packed here, eagerly: nothing is allocated or copied on the first call, which may be under graph capture
+            w1 = c3._w_as.setdefault(2, pack_as_weights(c3.w, 2))
+            if f32_out:                                        # <= 8 channels: zero rows up to one 128-channel slice of an A = 1 stream
+                wp = torch.zeros(128, 1, 1, c1.cin, device=c1.w.device, dtype=c1.w.dtype)
+                wp[:c1.cout] = c1.w
+                self.w = (w1, pack_as_weights(wp, 1))
+            else:
+                self.w = (w1, pack_as_weights(c1.w, 2))
+
+    def _desc(self, B, H, W, cbuf):
+        c3 = self.c3
+        return ConvDesc(B, H, W, c3.cin, cbuf, 0, c3.cout, c3.cout, 0, 0, 0, 3, 3, c3.stride, c3.pad, _dt(c3.dtype), _dt(c3.dtype), c3.flags & CONV_RELU, 0, 0, 1.0)
+
+    def __call__(self, x, out=None):
+        c3, c1 = self.c3, self.c1
+        B, H, W, cbuf = x.shape
+        if (self.w is None or not self.head_chain or x.dtype != c3.dtype or not x.is_contiguous() or getattr(_TLS, 'calibrating', False)
+                or (out is not None and (out.dtype != c1.out_dtype or out.shape != (B, H, W, c1.cout) or not out.is_contiguous()))):
+            return c1(c3(x), out=out)
+        d = self._desc(B, H, W, cbuf)
+        if not _capi.lib().dir_conv2d_as_chain_supported(d, c1.cout, _dt(c1.out_dtype)):
+            return c1(c3(x), out=out)
+        if out is None:
+            out = torch.empty(B, H, W, c1.cout, device=x.device, dtype=c1.out_dtype)
+        if getattr(_TLS, 'capture', None) is not None:       # autotune_energy: this call, replayable
+            _TLS.capture.append((self, (x,), dict(out=out)))
+        if _capi.PROFILE is not None:
+            m = B * H * W
+            _capi.annotate(family='conv', flops=2.0 * m * (c3.cout * c3.alg_k + c1.cout * c1.alg_k), op=c3, covers=(c1,), dtype='bf16',
+                           shape='M=%d N=%d K=%d k3x3 s1 + 1x1 -> %d' % (m, c3.cout, c3.alg_k, c1.cout),
+                           bytes=m * c3.cin * x.element_size() + (c3.w.numel() + c1.w.numel()) * c3.w.element_size() + m * c1.cout * out.element_size())
+        _capi.check(_capi.lib().dir_conv2d_as_chain_forward(d, _capi.ptr(x), _capi.ptr(self.w[0]), _capi.ptr(c3.scale), _capi.ptr(c3.shift),
+                                                            _capi.ptr(self.w[1]), _capi.ptr(c1.scale), _capi.ptr(c1.shift), c1.cout, 1 if c1.flags & CONV_RELU else 0,
+                                                            _capi.ptr(out), c1.cout, 0, _dt(c1.out_dtype), _capi.stream_ptr()), 'dir_conv2d_as_chain_forward')
+        return out
+
+
 class StageOp(object):
     """Joint2BoneFeature (models/dir.py:19-174) packed for one pyramid level"""
 
@@ -1150,6 +1205,9 @@ class DirEngine(object):
         self.final0.link_split(self.final3)
         self.final3.link_split(self.heads0)
         self.heads0.link_split(self.heads3)
+        # 16-bit storage: each 3x3 and the 1x1 that alone reads it as one launch (ConvChainOp; the link_split hand-over above is the f16-arithmetic modes')
+        self.final_chain = ConvChainOp(self.final0, self.final3)
+        self.heads_chain = ConvChainOp(self.heads0, self.heads3)
 
     # ------------------------------------------------------------------------------------------ pieces
     def init_regressor(self, c4):
@@ -1343,7 +1401,7 @@ class DirEngine(object):
         B = img.shape[0]
         saved_overlap, saved_profile = self.overlap, _capi.PROFILE
         self.overlap = False
-        best = {}
+        best, covers = {}, {}
         try:
             for v in self.CONV_VARIANTS:
                 if v in self.TUNE_EXCLUDE:
@@ -1353,6 +1411,7 @@ class DirEngine(object):
                 acc = {}
                 for rec in self._profiled_forwards(img, reps):
                     acc.setdefault(rec['op'], []).append(rec['e0'].elapsed_time(rec['e1']))
+                    covers[rec['op']] = rec.get('covers', ())
                 for op, ts in acc.items():
                     t = min(ts)
                     margin = self.PIPE_MARGIN if v in (8, 9, 10, 11, 12, 13, 14, 15) else self.STREAM_MARGIN if v in STREAM_VARIANTS else 0.03
@@ -1366,8 +1425,22 @@ class DirEngine(object):
             op.variant[B] = v
         self.tuned_batches.add(B)
         self._tuned_order = getattr(self, '_tuned_order', {})
-        self._tuned_order[B] = [op for op in best]          # first-call order of one forward: stable for a given engine
-        return {op: v for op, (t, v) in best.items()}
+        # first-call order of one forward: stable for a given engine.  One row per LAYER: a chained launch (ConvChainOp) is followed by the layers it
+        # covers, whose variant is carried (it is what they run with when the chain is off)
+        self._tuned_order[B] = self._layer_ops(dict(op=op, covers=covers.get(op, ())) for op in best)
+        for op in self._tuned_order[B]:
+            op.variant.setdefault(B, 0)
+        return {op: op.variant[B] for op in self._tuned_order[B]}
+
+    @staticmethod
+    def _layer_ops(recs):
+        """the conv-family layers behind profile records, in first-call order: a record's op, then the ops its launch covers"""
+        ops = []
+        for rec in recs:
+            for op in (rec['op'],) + tuple(rec.get('covers', ())):
+                if op not in ops:
+                    ops.append(op)
+        return ops
 
     def autotune_energy(self, img, seconds=None, slack=2.6, idle_w=None, log=None, max_calls=None, min_saving=0.0, near=1.12):
         """The per-layer kernel choice for THROUGHPUT with several forwards in flight.  Four bs-64 forwards in flight run the socket at its
@@ -1466,6 +1539,8 @@ class DirEngine(object):
                                  fastest_w=round(row[fastest][1])))
                 if log is not None:
                     log(rows[-1])
+                for c in ((op.c1,) if isinstance(op, ConvChainOp) else ()):       # a layer covered by a chained launch is not rated (no row in `layers`:
+                    c.variant.setdefault(B, 0)                                    # those are measurements); its variant is carried in the table
         finally:
             _TLS.capture, _TLS.variant = None, None
             self.overlap = saved_overlap
@@ -1499,10 +1574,7 @@ class DirEngine(object):
         B = img.shape[0]
         saved_overlap, saved_profile, self.overlap = self.overlap, _capi.PROFILE, False
         try:
-            ops = []
-            for rec in self._profiled_forwards(img, 1):
-                if rec['op'] not in ops:
-                    ops.append(rec['op'])
+            ops = self._layer_ops(self._profiled_forwards(img, 1))      # (a chained launch stands for every layer it covers)
         finally:
             _capi.PROFILE, self.overlap = saved_profile, saved_overlap
         if len(ops) != len(table) or any([op.cout, op.cin, op.kh, op.kw, op.stride] != row[:5] for op, row in zip(ops, table)):
@@ -1635,8 +1707,8 @@ class DirEngine(object):
             buf = nxt
         e3 = (self.res['enhance_layer3'] if nx == 0 else self.res_x[nx - 1])(buf)
         # ---- heads (models/dir.py:474-476)
-        feat = self.final3(self.final0(e3))
-        sd6 = self.heads3(self.heads0(feat))                                     # NHWC fp32 [B,32,32,6] = seg | dense
+        feat = self.final_chain(e3)
+        sd6 = self.heads_chain(feat)                                             # NHWC fp32 [B,32,32,6] = seg | dense
         seg, dense = sd6[..., :3], sd6[..., 3:]
         if taps is not None:
             taps.update(c1=c1, c2=c2, c3=c3, c4=c4, fusion4=enh4_in[..., :256], proj4=enh4_in[..., 256:], enh4=e4,

@@ -29,7 +29,7 @@ extern "C" {
 #define DIR_E_LAUNCH (-2)   /* hipLaunchKernel / HIP runtime error          */
 #define DIR_E_NODEVICE (-3) /* no gfx950 device visible                     */
 
-#define DIR_ABI_VERSION 47
+#define DIR_ABI_VERSION 48
 
 int dir_abi_version(void);
 const char* dir_last_error(void);
@@ -544,6 +544,25 @@ int dir_conv1x1_stream_forward(const dir_conv_desc* desc, const void* x, const d
 int dir_conv2d_as_supported(const dir_conv_desc* desc, int blocks_per_wave, int pixel_blocks);
 int dir_conv2d_as_forward(const dir_conv_desc* desc, const void* x, const void* w_as, const float* scale, const float* shift,
                           const void* residual, void* y, int blocks_per_wave, int pixel_blocks, void* stream);
+
+/* A 3x3 on the 32x32 map and the 1x1 that is its ONLY reader as one launch (conv_as.hip, the chained mode of the (2, 4) activation-stationary kernel):
+ * models/dir.py:474-476 conv_final (3x3 256 -> 256, BN, ReLU, then 1x1 256 -> 256 + bias) and models/dir.py:425-433 the seg / dense heads (3x3, BN, ReLU,
+ * then 1x1 -> 3 each; merged: 256 -> 6).  A workgroup owns 128 pixels x all 256 channels of the 3x3, so when its reduction ends it holds everything
+ * the 1x1 needs: the 3x3's map is rounded to the storage kind in registers -- t = act(scale * conv3x3(x) + shift), the arithmetic and saturation of
+ * dir_conv2d_as_forward's stores -- and kept in LDS as the B operand of a second K = 256 reduction; it never reaches memory.
+ *   y[..., out_coff .. + cout2] = act2(scale2 * (t . W2^T) + shift2),   act2 = ReLU when relu2 != 0
+ * Same K order and k-slot assignment as dir_conv2d_forward in both reductions: bit-identical to dir_conv2d_as_forward followed by dir_conv2d_forward.
+ * desc: the 3x3 (kh = kw = 3, pad 1, stride 1, W = 32, (H W) % 128 == 0, Cin % 64 == 0, Cout = 256, in_dtype = out_dtype = BF16 | F16, DIR_CONV_RELU as
+ * wanted; its output slice and residual fields are ignored -- there is no residual).  w_as: pack_as_weights(W, 2) as for dir_conv2d_as_forward.
+ * out_dtype = the storage kind: cout2 = 256, w2_as = pack_as_weights(W2 [256][1][1][256], 2), y 16-bit with out_cstride % 8 == out_coff % 8 == 0.
+ * out_dtype = DIR_DT_F32: cout2 in {2, 4, 6, 8}, w2_as = pack_as_weights(W2 zero-padded to [128][1][1][256], 1) (only wave 0's share, 16 KB, is read),
+ * y fp32 with out_cstride and out_coff even.  out_cstride 0 = cout2.  scale, scale2 (1), shift, shift2 (0) optional.
+ * dir_conv2d_as_chain_supported returns 1 when the pair qualifies (no launch); dir_conv2d_as_chain_forward returns DIR_E_INVALID before any launch for
+ * whatever it rejects. */
+int dir_conv2d_as_chain_supported(const dir_conv_desc* desc, int cout2, int out2_dtype);
+int dir_conv2d_as_chain_forward(const dir_conv_desc* desc, const void* x, const void* w_as, const float* scale, const float* shift,
+                                const void* w2_as, const float* scale2, const float* shift2, int cout2, int relu2,
+                                void* y, int out_cstride, int out_coff, int out_dtype, void* stream);
 
 /* a11 with a10's sparsity: same as dir_conv2d_forward (no prologue), plus group_bbox int32 [B][Cin/64][4] = for every
  * image and every 64-channel input group the pixel box (ymin,ymax,xmin,xmax) outside which that group is exactly zero.
