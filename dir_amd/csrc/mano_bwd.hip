@@ -33,13 +33,18 @@ struct ManoBwdHand {
 };
 struct ManoBwdArgs { ManoBwdHand h[2]; };
 
+// mag = the RAW magnitude |v| (the divisor is max(|v|, 1e-8)): the backward needs to know which branch of the clamp was taken
 __device__ __forceinline__ void normalize3b(float& x, float& y, float& z, float& mag) {
 #pragma clang fp contract(off)
-    mag = fmaxf(sqrtf(x * x + y * y + z * z), 1e-8f);
-    x /= mag; y /= mag; z /= mag;
+    mag = sqrtf(x * x + y * y + z * z);
+    const float m = fmaxf(mag, 1e-8f);
+    x /= m; y /= m; z /= m;
 }
-// n = v / max(|v|, 1e-8): g v = (g - n (n . g)) / |v|   (the clamp branch has zero measure on the path)
+// n = v / max(|v|, 1e-8): g v = (g - n (n . g)) / |v| where |v| >= 1e-8; in the clamped branch n = v / 1e-8 is linear in v and
+// g v = g / 1e-8 without the projection (rot6d.py:54-60 under autograd: torch.max passes no gradient to |v| there).  A column shorter
+// than 1e-8, or x^ - y^ of near-parallel columns, takes that branch.
 __device__ __forceinline__ void normalize3_bwd(float nx, float ny, float nz, float mag, float& gx, float& gy, float& gz) {
+    if (mag < 1e-8f) { gx /= 1e-8f; gy /= 1e-8f; gz /= 1e-8f; return; }
     const float d = nx * gx + ny * gy + nz * gz;
     gx = (gx - nx * d) / mag; gy = (gy - ny * d) / mag; gz = (gz - nz * d) / mag;
 }

@@ -113,6 +113,15 @@ def test_mano_reflection_assertion():
     p[0, :6] = torch.tensor([1., 0, 0, 0, 1, 0])
     m(p)                                   # fine
     assert m.check_reflection
+    # the flag itself, as tests/test_gpu_mano_sweep.py compares it: det < 0 of the float32 restatement's root, on every root class
+    import os
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), 'helpers'))
+    import mano_cases as MC
+    import mano_gpu_run as MR
+    for c in MC.forward_cases():
+        if c.jc == 'normal':
+            assert int(MR.forward_single([c])['flags'][0]) == MC.flag_f32(c), c.name
 
 
 def test_native_library_is_loaded():
