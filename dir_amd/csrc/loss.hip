@@ -11,6 +11,7 @@
 //     primitive of libdir_hip.so); the Jaccard scan runs one workgroup per class with a carried prefix.
 // Elementwise arithmetic is fp32 in the reference's operation order (contraction off); sums accumulate in fp64.
 // HBM-bound and tiny: 2 x (778 x 5 + ...) floats per sample and stage.
+#include <atomic>
 #include <cstring>
 
 #include "dir_common.h"
@@ -763,11 +764,15 @@ extern "C" int dir_stage_losses_backward(const dir_loss_pred* pred_host, const d
     StageBwdArgs a;
     a.p = *pred_host; a.g = *gt_host; a.o = *grads_host; a.gout = grad_out13; a.coord_weight = coord_weight; a.B = B;
     for (int h = 0; h < 2; ++h) { a.vf_off[h] = vert_face_offsets[h]; a.vf_idx[h] = vert_face_index[h]; }
-    static bool attr_set = false;
-    if (!attr_set) {
+    // the attribute belongs to the kernel's code object on ONE device: remembered per device (a process that steps on device 1 after device 0 must raise it there too)
+    constexpr int ATTR_DEVICES = 64;
+    static std::atomic<bool> attr_set[ATTR_DEVICES];      // zero-initialised; two threads may both set the attribute once, which is harmless
+    int dev = 0;
+    DIR_REQUIRE(hipGetDevice(&dev) == hipSuccess && dev >= 0, "dir_stage_losses_backward: no current device");
+    if (dev >= ATTR_DEVICES || !attr_set[dev].load(std::memory_order_acquire)) {
         DIR_REQUIRE(hipFuncSetAttribute((const void*)stage_loss_bwd_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) == hipSuccess,
                     "dir_stage_losses_backward: cannot raise the dynamic LDS limit");
-        attr_set = true;
+        if (dev < ATTR_DEVICES) attr_set[dev].store(true, std::memory_order_release);
     }
     DIR_LAUNCH(stage_loss_bwd_kernel, dim3(B, 2), dim3(LT), lds, (hipStream_t)stream, a);
     return check_launch("dir_stage_losses_backward");
