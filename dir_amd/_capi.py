@@ -141,7 +141,7 @@ class RenderLights(C.Structure):         # dir_render_lights
                 ('shininess', C.c_float)]
 
 
-ABI_VERSION = 48         # DIR_ABI_VERSION (include/dir_hip.h)
+ABI_VERSION = 49         # DIR_ABI_VERSION (include/dir_hip.h)
 DT_F32, DT_BF16, DT_F16X3, DT_F16X1, DT_F16X3P, DT_F16X1P, DT_F16 = 0, 1, 3, 4, 5, 6, 7      # DT_F16: f16 STORAGE (round 5)
 CONV_RELU, CONV_PRE_RELU = 1, 2
 
@@ -201,8 +201,6 @@ _SIGNATURES = {
                                           C.POINTER(TokenMlp), C.POINTER(TokenMlp), _p, _p, _i, _p]),
     'dir_pgcn_stack_forward': (C.c_int, [C.POINTER(PgcnLayer), _i, _p, _p, _p, C.c_longlong, _p, _i, _p]),
     'dir_pgcn_stack_forward_pair': (C.c_int, [C.POINTER(PgcnLayer), C.POINTER(PgcnLayer), _i, _p, _p, _p, _p, _i, _p]),
-    'dir_pgcn_fused_sync_bytes': (C.c_longlong, []),
-    'dir_pgcn_stack_forward_fused': (C.c_int, [C.POINTER(PgcnLayer), C.POINTER(PgcnLayer), _i, _p, _p, _p, _p, _p, _i, _i, _p]),
     'dir_ste_forward': (C.c_int, [C.POINTER(SteParams), _p, _p, _p, _i, _p]),
     'dir_regress_forward': (C.c_int, [C.POINTER(RegressParams), _p, _p, _p, _p, _p, _p, _p, _p, _i, _p]),
     'dir_bone_fusion_scratch_bytes': (C.c_size_t, [_i]),
@@ -234,10 +232,8 @@ _SIGNATURES = {
     'dir_bn_train_stats_from_partials': (C.c_int, [_p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, C.c_float, C.c_float, _p]),
     'dir_bn_train_apply': (C.c_int, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
     'dir_bn_train_forward_from_partials': (C.c_int, [_p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, C.c_float, C.c_float, _i, _p, _p]),
-    'dir_bn_one_launch_status': (C.c_int, []),
     'dir_upsample_nearest_add_f32': (C.c_int, [_p, _p, _i, _i, _i, _i, _i, _p]),
     'dir_upsample_nearest_backward_f32': (C.c_int, [_p, _p, _i, _i, _i, _i, _i, _p]),
-    'dir_bn_one_launch_enable': (C.c_int, [_i]),
     'dir_bn_train_backward': (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, C.c_longlong, _p]),
     'dir_bn_frozen_workspace_bytes': (C.c_longlong, [_i, _i]),
     'dir_bn_sync_workspace_bytes': (C.c_longlong, [_i, _i]),
@@ -303,7 +299,7 @@ _SIGNATURES = {
 #    + whatever the caller announced for this call with annotate(): 'flops', 'bytes' (algorithmic work), 'shape', 'op'}
 PROFILE = None
 _pending = {}
-_NO_PROFILE = ('dir_conv2d_as_supported', 'dir_conv2d_as_chain_supported', 'dir_residual_chain_supported', 'dir_abi_version', 'dir_bn_one_launch_status', 'dir_bn_one_launch_enable', 'dir_last_error', 'dir_device_info', 'dir_launch_log_reset', 'dir_launch_log_get', 'dir_launch_log_note',
+_NO_PROFILE = ('dir_conv2d_as_supported', 'dir_conv2d_as_chain_supported', 'dir_residual_chain_supported', 'dir_abi_version', 'dir_last_error', 'dir_device_info', 'dir_launch_log_reset', 'dir_launch_log_get', 'dir_launch_log_note',
                'dir_bone_fusion_scratch_bytes', 'dir_dense_losses_workspace_bytes', 'dir_dense_losses_backward_workspace_bytes',
                'dir_gemm_f32_splitk_workspace_bytes', 'dir_bn_train_workspace_bytes', 'dir_bn_sync_workspace_bytes', 'dir_bn_frozen_workspace_bytes', 'dir_jpeg_planes_bytes', 'dir_render_workspace_bytes', 'dir_render_adjacency_bytes', 'dir_render_shaded_workspace_bytes', 'dir_colsum_workspace_bytes', 'dir_conv2d_wgrad_workspace_bytes', 'dir_conv2d_wgrad_f16x3_workspace_bytes',
                'dir_one_euro_state_bytes')

@@ -1,21 +1,29 @@
-// Building blocks of the backward pass over the joint-token path (reference: train.py:66-70 runs
-// torch autograd through transformer/mixSTE.py, SemGCN/p_graph_conv.py and the nn.Conv1d / nn.Linear / nn.LayerNorm / nn.BatchNorm1d
-// modules of models/dir.py:19-130).  The token path is ~0.1 GFLOP per image: these are plain, exact-fp32, deterministic kernels
-// (fixed summation orders, no atomics) -- correctness and reproducibility first; they are composed by dir_amd/train/*.py.
+// The fp32 training operators: building blocks of the forward and backward passes in training mode (reference: train.py:66-70
+// runs torch autograd through transformer/mixSTE.py, SemGCN/p_graph_conv.py and the nn.Conv* / nn.Linear / nn.LayerNorm / nn.BatchNorm* modules of
+// models/dir.py:19-130).  Plain, exact-fp32, deterministic kernels (fixed summation orders, no atomics) -- correctness and reproducibility first;
+// they are composed by dir_amd/train/*.py.  Every launch here is one ordinary grid: no workgroup waits on another.
 //
-//   dir_gemm_f32              C = op(A) op(B) (+ bias | + C), batched / strided, exact fp32 on v_mfma_f32_16x16x4_f32
-//   dir_colsum_f32            bias gradients: column sums of a [R, N] matrix
+//   dir_gemm_f32 / _grouped / _splitk    C = op(A) op(B) (+ bias | + C), batched / strided, exact fp32 on v_mfma_f32_16x16x4_f32
+//   dir_colsum_f32                       bias gradients: column sums of a [R, N] matrix
 //   dir_layernorm_forward / _backward    nn.LayerNorm over the last dimension (mixSTE.py:177: eps 1e-6; head: 1e-5)
-//   dir_gelu_forward / _backward         exact-erf GELU (mixSTE.py:12,27)
+//   dir_gelu_* / dir_relu_*              exact-erf GELU (mixSTE.py:12,27), ReLU
 //   dir_attention_forward / _backward    softmax(q k^T * scale) v per (sample, head) (mixSTE.py:76-97)
-//   dir_bn_train_forward / _backward     BatchNorm1d / 2d in training mode over [R rows, C channels] (batch statistics, running update)
+//   dir_bn_train_*                       BatchNorm1d / 2d in training mode over [R rows, C channels] (batch statistics, running update): forward and
+//                                        backward, the statistics alone (_stats), the normalisation alone (_apply), and the *_from_partials forms that
+//                                        start from chunk partials a convolution's epilogue left
+//   dir_bn_sync_*                        the local parts of SyncBN (the collectives run between them)
+//   dir_bn_frozen_*                      BatchNorm with frozen statistics inside a training pass
+//     (the chunked BatchNorm entry points share one launch plan: BnPlan and the launch_bn_* helpers below)
+//   dir_upsample_nearest_add_f32 / _backward_f32, dir_pgcn_adjacency_*, dir_grid_rows_*, dir_stage_positions      the small operators of the
+//                                        HRNet fuse layers, the P-GCN adjacency, the joint feature rows and the stage positions
+//   dir_axpy_f32 / _multi_f32            dst += alpha src, over one tensor or a table of them in one launch
+//   dir_conv2d_wgrad_f32                 the exact-fp32 weight gradient of a convolution
 #include "dir_common.h"
 #include "dir_mfma.h"
 
 #include <math.h>
 #include <stdlib.h>
 #include <initializer_list>
-#include <mutex>
 
 namespace {
 
@@ -725,44 +733,11 @@ __global__ __launch_bounds__(256) void bn_partial4_kernel(const float* x, const 
         if (mode == 2) *reinterpret_cast<float4*>(p2 + (long long)ch * C + c) = u;
     }
 }
-// Loads and stores that are coherent across the GPU's eight L2s WITHOUT a fence (agent-scope monotonic: `sc1` on gfx950): what workgroups of one
-// launch hand each other (the one-launch BatchNorm below).  CO = false: plain accesses.
-template <bool CO> __device__ __forceinline__ float ld_co(const float* p) {
-    if constexpr (CO) return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else return *p;
-}
-template <bool CO> __device__ __forceinline__ void st_co(float* p, float v) {
-    if constexpr (CO) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else *p = v;
-}
-template <bool CO> __device__ __forceinline__ float4 ld_co4(const float* p) {
-    if constexpr (CO) return make_float4(ld_co<true>(p), ld_co<true>(p + 1), ld_co<true>(p + 2), ld_co<true>(p + 3));
-    else return *reinterpret_cast<const float4*>(p);
-}
-template <bool CO> __device__ __forceinline__ void st_co4(float* p, const float4 v) {
-    if constexpr (CO) { st_co<true>(p, v.x); st_co<true>(p + 1, v.y); st_co<true>(p + 2, v.z); st_co<true>(p + 3, v.w); }
-    else *reinterpret_cast<float4*>(p) = v;
-}
-// dir::sum_in_order (the same order, the same bits) over coherent loads
-template <bool CO> __device__ __forceinline__ float sum_in_order_co(const float* p, long long stride, int n, float s) {
-    if constexpr (!CO) return dir::sum_in_order(p, stride, n, s);
-    int c = 0;
-    for (; c + 8 <= n; c += 8) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = ld_co<true>(p + (long long)(c + u) * stride);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) s += v[u];
-    }
-    for (; c < n; ++c) s += ld_co<true>(p + (long long)c * stride);
-    return s;
-}
 // sums of the chunk partials: a workgroup = 16 channels x 16 lanes (lane l adds chunks l, l + 16, ... in order; lanes combined in lane order)
-template <bool CO = false>
 __device__ __forceinline__ float chunk_sum16(const float* p, int chunks, int C, int c, float (&s)[16][17]) {
     const int cl = threadIdx.x & 15, rl = threadIdx.x >> 4;
     float a = 0.f;
-    if (c < C && rl < chunks) a = sum_in_order_co<CO>(p + (long long)rl * C + c, 16ll * C, (chunks - rl + 15) / 16, a);
+    if (c < C && rl < chunks) a = dir::sum_in_order(p + (long long)rl * C + c, 16ll * C, (chunks - rl + 15) / 16, a);
     s[rl][cl] = a;
     __syncthreads();
     float t = 0.f;
@@ -823,9 +798,9 @@ __global__ __launch_bounds__(256) void zero_f32_kernel(float* p, int n) {
 // ---- 16-byte versions for C % 4 == 0 (every BatchNorm2d of the path).  Forward statistics in ONE pass over HBM: a workgroup (64 channels x
 // one 256-row chunk) forms the chunk's column sums, then the squared deviations from the CHUNK mean on a second read that hits L2 (a chunk
 // is 64 KB); the finalise kernel combines the chunks exactly: var = sum_k [M2_k + n_k (mean_k - mean)^2] / R, in chunk order.
-template <bool CO = false>
-__device__ __forceinline__ void bn_stats4_tile(const float* x, float* p1, float* p2, int R, int C, int ld, int cg, int ch, float4 (&s1)[16][16]) {
-    const int cq = threadIdx.x & 15, rl = threadIdx.x >> 4, c = cg * 64 + cq * 4;
+__global__ __launch_bounds__(256) void bn_stats4_kernel(const float* x, float* p1, float* p2, int R, int C, int ld) {
+    __shared__ float4 s1[16][16];
+    const int cq = threadIdx.x & 15, rl = threadIdx.x >> 4, c = blockIdx.x * 64 + cq * 4, ch = blockIdx.y;
     const int r0 = ch * BN_CHUNK_ROWS, r1 = min(R, r0 + BN_CHUNK_ROWS);
     const bool on = c < C;
     float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -871,36 +846,40 @@ __device__ __forceinline__ void bn_stats4_tile(const float* x, float* p1, float*
     if (rl == 0 && on) {
         float4 u = s1[0][cq];
         for (int l = 1; l < 16; ++l) { const float4 q = s1[l][cq]; u.x += q.x; u.y += q.y; u.z += q.z; u.w += q.w; }
-        st_co4<CO>(p1 + (long long)ch * C + c, t);
-        st_co4<CO>(p2 + (long long)ch * C + c, u);
+        *reinterpret_cast<float4*>(p1 + (long long)ch * C + c) = t;
+        *reinterpret_cast<float4*>(p2 + (long long)ch * C + c) = u;
     }
 }
-__global__ __launch_bounds__(256) void bn_stats4_kernel(const float* x, float* p1, float* p2, int R, int C, int ld) {
-    __shared__ float4 s1[16][16];
-    bn_stats4_tile(x, p1, p2, R, C, ld, blockIdx.x, blockIdx.y, s1);
-}
-// the statistics of 16 channels (c16 = first channel / 16) from the chunk partials
-template <bool CO = false>
-__device__ __forceinline__ void bn_stats_combine16(const float* p1, const float* p2, float* save_mean, float* save_rstd, float* running_mean,
-                                                   float* running_var, int chunks, int R, int C, float eps, float momentum, int c16, float (&s)[16][17],
-                                                   int crows = BN_CHUNK_ROWS) {
-    const int cl = threadIdx.x & 15, rl = threadIdx.x >> 4, c = c16 * 16 + cl;
-    const float mu = chunk_sum16<CO>(p1, chunks, C, c, s) / R;
+// mean and M2 = sum (x - mean)^2 of channel c (a workgroup = 16 channels x 16 lanes, like chunk_sum16) from the chunk partials, pooled exactly in chunk
+// order; true in the one thread per channel that holds them (lane 0 of a channel below C)
+__device__ __forceinline__ bool bn_chunks_mean_m2(const float* p1, const float* p2, int chunks, int R, int C, int c, int crows, float (&s)[16][17], float& mu,
+                                                  float& q) {
+    const int cl = threadIdx.x & 15, rl = threadIdx.x >> 4;
+    mu = chunk_sum16(p1, chunks, C, c, s) / R;
     __syncthreads();
     float a = 0.f;
     if (c < C)
         for (int k = rl; k < chunks; k += 16) {
             const int nk = min(crows, R - k * crows);
-            const float d = ld_co<CO>(p1 + (long long)k * C + c) / nk - mu;
-            a += fmaf((float)nk * d, d, ld_co<CO>(p2 + (long long)k * C + c));
+            const float d = p1[(long long)k * C + c] / nk - mu;
+            a += fmaf((float)nk * d, d, p2[(long long)k * C + c]);
         }
     s[rl][cl] = a;
     __syncthreads();
-    if (rl != 0 || c >= C) return;
-    float q = 0.f;
+    if (rl != 0 || c >= C) return false;
+    q = 0.f;
     for (int l = 0; l < 16; ++l) q += s[l][cl];
+    return true;
+}
+// the statistics of the workgroup's 16 channels from the chunk partials
+__device__ __forceinline__ void bn_stats_combine16(const float* p1, const float* p2, float* save_mean, float* save_rstd, float* running_mean,
+                                                   float* running_var, int chunks, int R, int C, float eps, float momentum, float (&s)[16][17],
+                                                   int crows = BN_CHUNK_ROWS) {
+    const int c = blockIdx.x * 16 + (threadIdx.x & 15);
+    float mu, q;
+    if (!bn_chunks_mean_m2(p1, p2, chunks, R, C, c, crows, s, mu, q)) return;
     const float var = q / R;
-    st_co<CO>(save_mean + c, mu); st_co<CO>(save_rstd + c, 1.f / sqrtf(var + eps));
+    save_mean[c] = mu; save_rstd[c] = 1.f / sqrtf(var + eps);
     if (running_mean) {
         running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * mu;
         running_var[c] = (1.f - momentum) * running_var[c] + momentum * (R > 1 ? q / (R - 1) : var);
@@ -909,7 +888,7 @@ __device__ __forceinline__ void bn_stats_combine16(const float* p1, const float*
 __global__ __launch_bounds__(256) void bn_stats_combine_kernel(const float* p1, const float* p2, float* save_mean, float* save_rstd, float* running_mean,
                                                               float* running_var, int chunks, int R, int C, float eps, float momentum) {
     __shared__ float s[16][17];
-    bn_stats_combine16(p1, p2, save_mean, save_rstd, running_mean, running_var, chunks, R, C, eps, momentum, blockIdx.x, s);
+    bn_stats_combine16(p1, p2, save_mean, save_rstd, running_mean, running_var, chunks, R, C, eps, momentum, s);
 }
 // round 5 (dir_bn_train_stats): the statistics only, plus the affine form the CONSUMING convolution applies where it reads the map --
 // pre_scale = gamma rstd, pre_shift = beta - mean gamma rstd (dir_conv2d_forward's pre-activation, dir_split_f16_forward's, dir_conv2d_wgrad_f16x3_pre's):
@@ -918,7 +897,7 @@ __global__ __launch_bounds__(256) void bn_stats_combine_pre_kernel(const float* 
                                                                   float* pre_scale, float* pre_shift, float* running_mean, float* running_var, int chunks, int R, int C,
                                                                   float eps, float momentum, int crows) {
     __shared__ float s[16][17];
-    bn_stats_combine16(p1, p2, save_mean, save_rstd, running_mean, running_var, chunks, R, C, eps, momentum, blockIdx.x, s, crows);
+    bn_stats_combine16(p1, p2, save_mean, save_rstd, running_mean, running_var, chunks, R, C, eps, momentum, s, crows);
     const int cl = threadIdx.x & 15, rl = threadIdx.x >> 4, c = blockIdx.x * 16 + cl;
     if (rl != 0 || c >= C || !pre_scale) return;         // (the thread that wrote save_mean[c] / save_rstd[c] above)
     const float g = w ? w[c] : 1.f, be = b ? b[c] : 0.f, k = g * save_rstd[c];
@@ -930,22 +909,9 @@ __global__ __launch_bounds__(256) void bn_stats_combine_pre_kernel(const float* 
 // channel from the same chunk partials as bn_stats_combine_kernel, combined in the same (chunk) order.
 __global__ __launch_bounds__(256) void bn_stats_local_kernel(const float* p1, const float* p2, float* mean_out, float* m2_out, int chunks, int R, int C) {
     __shared__ float s[16][17];
-    const int cl = threadIdx.x & 15, rl = threadIdx.x >> 4, c = blockIdx.x * 16 + cl;
-    const float mu = chunk_sum16(p1, chunks, C, c, s) / R;
-    __syncthreads();
-    float a = 0.f;
-    if (c < C)
-        for (int k = rl; k < chunks; k += 16) {
-            const int nk = min(BN_CHUNK_ROWS, R - k * BN_CHUNK_ROWS);
-            const float d = p1[(long long)k * C + c] / nk - mu;
-            a += fmaf((float)nk * d, d, p2[(long long)k * C + c]);
-        }
-    s[rl][cl] = a;
-    __syncthreads();
-    if (rl != 0 || c >= C) return;
-    float q = 0.f;
-    for (int l = 0; l < 16; ++l) q += s[l][cl];
-    mean_out[c] = mu; m2_out[c] = q;
+    const int c = blockIdx.x * 16 + (threadIdx.x & 15);
+    float mu, q;
+    if (bn_chunks_mean_m2(p1, p2, chunks, R, C, c, BN_CHUNK_ROWS, s, mu, q)) { mean_out[c] = mu; m2_out[c] = q; }
 }
 // The ranks' parts [W][2 C + 4] = (mean_r [C] | M2_r [C] | rows_r, 0, 0, 0), gathered in rank order, pooled exactly (Chan): n = sum n_r,
 // mean = sum n_r mean_r / n, M2 = sum [M2_r + n_r (mean_r - mean)^2]; every rank runs this on the same gathered bytes -> the same statistics
@@ -1004,11 +970,10 @@ __global__ __launch_bounds__(256) void bn_apply_fwd4_kernel(const float* x, cons
     }
 }
 // backward partial sums (the vec4 form of bn_partial_kernel's mode 2) with the ReLU mask re-computed from x
-template <bool CO = false>
-__device__ __forceinline__ void bn_bwd_partial4_tile(const float* x, const float* gy, const float* w, const float* b, const float* mu, const float* rs,
-                                                     float* p1, float* p2, int R, int C, int ld, int relu, int cg, int ch, float4 (&s1)[16][16],
-                                                     float4 (&s2)[16][16]) {
-    const int cq = threadIdx.x & 15, rl = threadIdx.x >> 4, c = cg * 64 + cq * 4;
+__global__ __launch_bounds__(256) void bn_bwd_partial4_kernel(const float* x, const float* gy, const float* w, const float* b, const float* mu, const float* rs,
+                                                             float* p1, float* p2, int R, int C, int ld, int relu) {
+    __shared__ float4 s1[16][16], s2[16][16];
+    const int cq = threadIdx.x & 15, rl = threadIdx.x >> 4, c = blockIdx.x * 64 + cq * 4, ch = blockIdx.y;
     const int r0 = ch * BN_CHUNK_ROWS, r1 = min(R, r0 + BN_CHUNK_ROWS);
     float4 a = make_float4(0.f, 0.f, 0.f, 0.f), bb = a;
     if (c < C) {
@@ -1049,31 +1014,21 @@ __device__ __forceinline__ void bn_bwd_partial4_tile(const float* x, const float
             t.x += q.x; t.y += q.y; t.z += q.z; t.w += q.w;
             u.x += z.x; u.y += z.y; u.z += z.z; u.w += z.w;
         }
-        st_co4<CO>(p1 + (long long)ch * C + c, t);
-        st_co4<CO>(p2 + (long long)ch * C + c, u);
+        *reinterpret_cast<float4*>(p1 + (long long)ch * C + c) = t;
+        *reinterpret_cast<float4*>(p2 + (long long)ch * C + c) = u;
     }
 }
-__global__ __launch_bounds__(256) void bn_bwd_partial4_kernel(const float* x, const float* gy, const float* w, const float* b, const float* mu, const float* rs,
-                                                             float* p1, float* p2, int R, int C, int ld, int relu) {
-    __shared__ float4 s1[16][16], s2[16][16];
-    bn_bwd_partial4_tile(x, gy, w, b, mu, rs, p1, p2, R, C, ld, relu, blockIdx.x, blockIdx.y, s1, s2);
-}
 // both column sums of the backward pass in one launch: t1 = g b, t2 = g w (also kept for the apply kernel)
-template <bool CO = false>
-__device__ __forceinline__ void bn_bwd_combine16(const float* p1, const float* p2, float* t1, float* t2, float* gb, float* gw, int chunks, int C, int c16,
-                                                 float (&s)[16][17]) {
-    const int c = c16 * 16 + (threadIdx.x & 15);
-    const float a = chunk_sum16<CO>(p1, chunks, C, c, s);
-    __syncthreads();
-    const float b = chunk_sum16<CO>(p2, chunks, C, c, s);
-    if ((threadIdx.x >> 4) != 0 || c >= C) return;
-    st_co<CO>(t1 + c, a); st_co<CO>(t2 + c, b);
-    if (gb) gb[c] = a;
-    if (gw) gw[c] = b;
-}
 __global__ __launch_bounds__(256) void bn_bwd_combine_kernel(const float* p1, const float* p2, float* t1, float* t2, float* gb, float* gw, int chunks, int C) {
     __shared__ float s[16][17];
-    bn_bwd_combine16(p1, p2, t1, t2, gb, gw, chunks, C, blockIdx.x, s);
+    const int c = blockIdx.x * 16 + (threadIdx.x & 15);
+    const float a = chunk_sum16(p1, chunks, C, c, s);
+    __syncthreads();
+    const float b = chunk_sum16(p2, chunks, C, c, s);
+    if ((threadIdx.x >> 4) != 0 || c >= C) return;
+    t1[c] = a; t2[c] = b;
+    if (gb) gb[c] = a;
+    if (gw) gw[c] = b;
 }
 __global__ __launch_bounds__(256) void bn_apply_bwd4_kernel(const float* gy, const float* x, const float* w, const float* b, const float* mu, const float* rs,
                                                            const float* s1, const float* s2, float* gx, int R, int C, int ld, int relu, float n_pool = 0.f) {
@@ -1145,181 +1100,6 @@ __global__ __launch_bounds__(256) void upsample_nearest_bwd_kernel(const float* 
             a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
         }
     *reinterpret_cast<float4*>(gx + p * C + c) = a;
-}
-
-// ---- BatchNorm over more than BN_SMALL_R rows in ONE launch (round 5; VERDICT r4 item 3: "BatchNorm out of its six launches").  The three
-// launches above (chunk partials -> combine -> apply) are dependent and small: at 32 images per GPU a launch boundary (~5 us) costs as much as
-// the median BatchNorm kernel runs, 660 of the step's 2 440 launches.  Here a PERSISTENT grid (every workgroup resident: grid <= what the GPU
-// holds) walks the same (64 channels x 256 rows) tiles; a channel group's statistics are combined by the workgroup whose tile arrives LAST
-// at the group's counter (in chunk order whatever the arrival order: the same bits as bn_stats_combine_kernel), the others wait on the
-// group's flag -- NOT on a grid-wide barrier: a 64-channel group is ready as soon as its own chunks are -- and then normalise the tiles they read.
-// words: [arrive | flag | depart][BN_ONE_GROUPS] + an error word, zero before the launch and zero again after it (the last tile to leave a
-// group clears it), owned by the library per stream (bn_one_words).  Visibility across the 8 XCDs' L2s: everything workgroups hand each other
-// (chunk partials, the group's statistics, the words) moves through agent-scope monotonic loads / stores (`sc1`: ld_co / st_co) ordered by
-// s_waitcnt vmcnt(0) -- NOT through release / acquire fences: a fence writes back / invalidates the XCD's whole L2, and one per tile made the
-// first version of this kernel a third SLOWER than the three launches (0.041 against 0.031 s per step).
-// MEASURED (MI355X, 32 images, profiles/r05_bn_one_launch_ab.txt): the same bits as the three launches, 220 launches instead of 660 per step -- and
-// 0.0325 s per step against 0.0315 s.  At this batch a launch boundary inside a busy stream costs ~1 us (the next dispatch is staged while the
-// previous kernel drains), less than what the one launch loses: every workgroup of a 64-channel group idles while ONE workgroup combines the
-// group's chunks (the combine kernel spreads that over C / 16 workgroups), and the grid is 3/4 of what fits.  So it is OFF by default
-// (DIR_BN_ONE_LAUNCH=1 / dir_bn_one_launch_enable(1) turns it on); what BatchNorm costs the step is its 6 passes over the feature maps, which only
-// the producing / consuming convolutions can absorb.
-constexpr int BN_ONE_GROUPS = 256, BN_ONE_WORDS = 3 * BN_ONE_GROUPS + 4;
-struct BnOne {
-    const float *x, *gy, *w, *b, *res;
-    float *y, *gx, *save_mean, *save_rstd, *running_mean, *running_var, *gw, *gb, *p1, *p2, *t1, *t2;
-    int* words;
-    int R, C, ld, relu, chunks, cgroups;
-    float eps, momentum;
-};
-__device__ __forceinline__ void bn_one_stores_done() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ int bn_one_arrive(int* counter) {
-    __shared__ int old;
-    bn_one_stores_done();              // this thread's coherent stores have reached memory
-    __syncthreads();                   // ... every thread's
-    if (threadIdx.x == 0) old = __hip_atomic_fetch_add(counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    return old;
-}
-__device__ __forceinline__ void bn_one_wait(int* flag, int* err) {
-    if (threadIdx.x == 0) {
-        const long long t0 = wall_clock64();
-        while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) {
-            __builtin_amdgcn_s_sleep(8);
-            if (wall_clock64() - t0 > 400000000ll) {                 // 4 s at 100 MHz: a workgroup of this launch never ran (see dir_bn_one_launch_status)
-                __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                break;
-            }
-        }
-    }
-    __syncthreads();                   // the statistics are then read with ld_co (from memory, not from this XCD's L2)
-}
-__device__ __forceinline__ void bn_one_leave(int* depart, int* flag, int chunks) {
-    __syncthreads();
-    if (threadIdx.x == 0 && __hip_atomic_fetch_add(depart, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == chunks - 1) {
-        __hip_atomic_store(flag, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // every tile of the group has seen the flag: clean for the next launch
-        __hip_atomic_store(depart, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-__global__ __launch_bounds__(256) void bn_one_fwd_kernel(const BnOne a) {
-    __shared__ float4 s1[16][16];
-    __shared__ float s[16][17];
-    const int ntile = a.cgroups * a.chunks, G = gridDim.x;
-    int *arrive = a.words, *flag = a.words + BN_ONE_GROUPS, *depart = a.words + 2 * BN_ONE_GROUPS, *err = a.words + 3 * BN_ONE_GROUPS;
-    for (int t = blockIdx.x; t < ntile; t += G) {
-        const int cg = t % a.cgroups, ch = t / a.cgroups;
-        __syncthreads();
-        bn_stats4_tile<true>(a.x, a.p1, a.p2, a.R, a.C, a.ld, cg, ch, s1);
-        if (bn_one_arrive(arrive + cg) != a.chunks - 1) continue;
-        for (int j = 0; j < 4; ++j) {                                  // the last tile of the group: every chunk partial of these 64 channels is in memory
-            __syncthreads();
-            bn_stats_combine16<true>(a.p1, a.p2, a.save_mean, a.save_rstd, a.running_mean, a.running_var, a.chunks, a.R, a.C, a.eps, a.momentum, cg * 4 + j, s);
-        }
-        bn_one_stores_done();
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            __hip_atomic_store(arrive + cg, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(flag + cg, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    const int cq = threadIdx.x & 15, rl = threadIdx.x >> 4;
-    const float4 one = make_float4(1.f, 1.f, 1.f, 1.f), zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int t = blockIdx.x; t < ntile; t += G) {
-        const int cg = t % a.cgroups, ch = t / a.cgroups, c = cg * 64 + cq * 4;
-        bn_one_wait(flag + cg, err);
-        if (c < a.C) {
-            const float4 m = ld_co4<true>(a.save_mean + c), k = ld_co4<true>(a.save_rstd + c);
-            const float4 g = a.w ? *reinterpret_cast<const float4*>(a.w + c) : one, be = a.b ? *reinterpret_cast<const float4*>(a.b + c) : zero;
-            const int r1 = min(a.R, (ch + 1) * BN_CHUNK_ROWS);
-            auto put = [&](int r, const float4 v, const float4 q) {
-                float4 o = make_float4(bn_value(v.x, m.x, k.x, g.x, be.x), bn_value(v.y, m.y, k.y, g.y, be.y), bn_value(v.z, m.z, k.z, g.z, be.z),
-                                       bn_value(v.w, m.w, k.w, g.w, be.w));
-                if (a.res) { o.x += q.x; o.y += q.y; o.z += q.z; o.w += q.w; }
-                if (a.relu) o = make_float4(fmaxf(o.x, 0.f), fmaxf(o.y, 0.f), fmaxf(o.z, 0.f), fmaxf(o.w, 0.f));
-                *reinterpret_cast<float4*>(a.y + (long long)r * a.ld + c) = o;
-            };
-            int r = ch * BN_CHUNK_ROWS + rl;
-            for (; r + 48 < r1; r += 64) {
-                float4 v[4], q[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    v[u] = *reinterpret_cast<const float4*>(a.x + (long long)(r + 16 * u) * a.ld + c);
-                    q[u] = a.res ? *reinterpret_cast<const float4*>(a.res + (long long)(r + 16 * u) * a.ld + c) : zero;
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) put(r + 16 * u, v[u], q[u]);
-            }
-            for (; r < r1; r += 16)
-                put(r, *reinterpret_cast<const float4*>(a.x + (long long)r * a.ld + c),
-                    a.res ? *reinterpret_cast<const float4*>(a.res + (long long)r * a.ld + c) : zero);
-        }
-        bn_one_leave(depart + cg, flag + cg, a.chunks);
-    }
-}
-__global__ __launch_bounds__(256) void bn_one_bwd_kernel(const BnOne a) {
-    __shared__ float4 s1[16][16], s2[16][16];
-    __shared__ float s[16][17];
-    const int ntile = a.cgroups * a.chunks, G = gridDim.x;
-    int *arrive = a.words, *flag = a.words + BN_ONE_GROUPS, *depart = a.words + 2 * BN_ONE_GROUPS, *err = a.words + 3 * BN_ONE_GROUPS;
-    for (int t = blockIdx.x; t < ntile; t += G) {
-        const int cg = t % a.cgroups, ch = t / a.cgroups;
-        __syncthreads();
-        bn_bwd_partial4_tile<true>(a.x, a.gy, a.w, a.b, a.save_mean, a.save_rstd, a.p1, a.p2, a.R, a.C, a.ld, a.relu, cg, ch, s1, s2);
-        if (bn_one_arrive(arrive + cg) != a.chunks - 1) continue;
-        for (int j = 0; j < 4; ++j) {
-            __syncthreads();
-            bn_bwd_combine16<true>(a.p1, a.p2, a.t1, a.t2, a.gb, a.gw, a.chunks, a.C, cg * 4 + j, s);
-        }
-        bn_one_stores_done();
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            __hip_atomic_store(arrive + cg, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (a.gx) __hip_atomic_store(flag + cg, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    if (!a.gx) return;
-    const int cq = threadIdx.x & 15, rl = threadIdx.x >> 4;
-    const float4 one = make_float4(1.f, 1.f, 1.f, 1.f), zero = make_float4(0.f, 0.f, 0.f, 0.f);
-    const float nn = (float)a.R;
-    for (int t = blockIdx.x; t < ntile; t += G) {
-        const int cg = t % a.cgroups, ch = t / a.cgroups, c = cg * 64 + cq * 4;
-        bn_one_wait(flag + cg, err);
-        if (c < a.C) {
-            const float4 m = *reinterpret_cast<const float4*>(a.save_mean + c), k = *reinterpret_cast<const float4*>(a.save_rstd + c);
-            const float4 g = a.w ? *reinterpret_cast<const float4*>(a.w + c) : one, be = a.b ? *reinterpret_cast<const float4*>(a.b + c) : zero;
-            const float4 a1 = ld_co4<true>(a.t1 + c), a2 = ld_co4<true>(a.t2 + c);
-            const float4 m1 = make_float4(a1.x / nn, a1.y / nn, a1.z / nn, a1.w / nn), m2 = make_float4(a2.x / nn, a2.y / nn, a2.z / nn, a2.w / nn);
-            const int r1 = min(a.R, (ch + 1) * BN_CHUNK_ROWS);
-            auto put = [&](int r, const float4 v, float4 q) {             // the expressions of bn_apply_bwd4_kernel
-                if (a.relu) {
-                    if (!(bn_value(v.x, m.x, k.x, g.x, be.x) > 0.f)) q.x = 0.f;
-                    if (!(bn_value(v.y, m.y, k.y, g.y, be.y) > 0.f)) q.y = 0.f;
-                    if (!(bn_value(v.z, m.z, k.z, g.z, be.z) > 0.f)) q.z = 0.f;
-                    if (!(bn_value(v.w, m.w, k.w, g.w, be.w) > 0.f)) q.w = 0.f;
-                }
-                float4 o;
-                o.x = g.x * k.x * (q.x - m1.x - (v.x - m.x) * k.x * m2.x);
-                o.y = g.y * k.y * (q.y - m1.y - (v.y - m.y) * k.y * m2.y);
-                o.z = g.z * k.z * (q.z - m1.z - (v.z - m.z) * k.z * m2.z);
-                o.w = g.w * k.w * (q.w - m1.w - (v.w - m.w) * k.w * m2.w);
-                *reinterpret_cast<float4*>(a.gx + (long long)r * a.ld + c) = o;
-            };
-            int r = ch * BN_CHUNK_ROWS + rl;
-            for (; r + 48 < r1; r += 64) {
-                float4 v[4], q[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    v[u] = *reinterpret_cast<const float4*>(a.x + (long long)(r + 16 * u) * a.ld + c);
-                    q[u] = *reinterpret_cast<const float4*>(a.gy + (long long)(r + 16 * u) * a.ld + c);
-                }
-#pragma unroll
-                for (int u = 0; u < 4; ++u) put(r + 16 * u, v[u], q[u]);
-            }
-            for (; r < r1; r += 16)
-                put(r, *reinterpret_cast<const float4*>(a.x + (long long)r * a.ld + c), *reinterpret_cast<const float4*>(a.gy + (long long)r * a.ld + c));
-        }
-        bn_one_leave(depart + cg, flag + cg, a.chunks);
-    }
 }
 
 // ---- BatchNorm over at most BN_SMALL_R rows as a COOPERATIVE kernel (round 4): the kernels above walk a channel's rows with one thread, three
@@ -1788,6 +1568,51 @@ static void launch_bn_partial(dim3 grid, hipStream_t s, const float* x, const fl
     else DIR_LAUNCH(bn_partial_kernel, grid, dim3(256), 0, s, x, gy, mu, rs, p1, p2, R, C, ld, mode, (const float*)nullptr, (const float*)nullptr, 0);
 }
 
+// The launch plan of the chunked BatchNorm entry points (more than BN_SMALL_R rows, SyncBN, frozen statistics): the chunk count, the grids over
+// (64 channels x one chunk) tiles and over 16-channel groups, and the workspace layout p1 [chunks][C] | p2 [chunks][C] | t1 [C] | t2 [C] as offsets in
+// floats (p1 at 0; the *_workspace_bytes functions are `end` or, without the two sums, `t1`).
+static int bn_chunks(int R) { return (R + BN_CHUNK_ROWS - 1) / BN_CHUNK_ROWS; }
+struct BnPlan {
+    int chunks;
+    dim3 pg, cg;
+    long long p2, t1, t2, end;
+};
+static BnPlan bn_plan(int R, int C) {
+    BnPlan p;
+    p.chunks = bn_chunks(R);
+    p.pg = dim3((C + 63) / 64, p.chunks); p.cg = dim3((C + 15) / 16);
+    p.p2 = (long long)p.chunks * C; p.t1 = 2 * p.p2; p.t2 = p.t1 + C; p.end = p.t2 + C;
+    return p;
+}
+// y = act(BatchNorm(x) + res) from the statistics; vec: what bn_vec4 said of the entry point's pointers
+static void launch_bn_apply_fwd(hipStream_t s, bool vec, const float* x, const float* w, const float* b, const float* mu, const float* rs, float* y, int R, int C, int ld,
+                                int relu, const float* res) {
+    if (vec) {
+        const long long nt = (long long)((R + 3) / 4) * (C / 4);
+        DIR_LAUNCH(bn_apply_fwd4_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, x, w, b, mu, rs, y, R, C, ld, relu, res);
+    } else {
+        const long long n = (long long)R * C;
+        DIR_LAUNCH(bn_apply_fwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, w, b, mu, rs, y, n, C, ld, relu, res);
+    }
+}
+// the backward chunk partials p1 = sum g, p2 = sum g xhat (g = gy under the ReLU mask)
+static void launch_bn_bwd_partial(hipStream_t s, bool vec, dim3 pg, const float* x, const float* gy, const float* w, const float* b, const float* mu, const float* rs,
+                                  float* p1, float* p2, int R, int C, int ld, int relu) {
+    if (vec) DIR_LAUNCH(bn_bwd_partial4_kernel, pg, dim3(256), 0, s, x, gy, w, b, mu, rs, p1, p2, R, C, ld, relu);
+    else launch_bn_partial(pg, s, x, gy, mu, rs, p1, p2, R, C, ld, 2, w, b, relu);
+}
+// g x from the two column sums; n_pool > 0 (SyncBN, vec only): the sums were pooled over that many rows
+static void launch_bn_apply_bwd(hipStream_t s, bool vec, const float* gy, const float* x, const float* w, const float* b, const float* mu, const float* rs,
+                                const float* t1, const float* t2, float* gx, int R, int C, int ld, int relu, float n_pool = 0.f) {
+    if (vec) {
+        const long long nt = (long long)((R + 3) / 4) * (C / 4);
+        DIR_LAUNCH(bn_apply_bwd4_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, gy, x, w, b, mu, rs, t1, t2, gx, R, C, ld, relu, n_pool);
+    } else {
+        const long long n = (long long)R * C;
+        DIR_LAUNCH(bn_apply_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, gy, x, w, b, mu, rs, t1, t2, gx, n, R, C, ld, relu);
+    }
+}
+
 }  // namespace
 
 extern "C" int dir_gemm_f32(const dir_gemm_desc* d, const float* A, const float* B, const float* bias, float* C, void* stream) {
@@ -1849,7 +1674,7 @@ extern "C" int dir_gemm_f32_splitk(const dir_gemm_desc* d, const float* A, const
 
 extern "C" long long dir_colsum_workspace_bytes(int R, int N) {
     if (R <= 0 || N <= 0) return -1;
-    return R <= BN_SMALL_R ? 0 : (long long)((R + BN_CHUNK_ROWS - 1) / BN_CHUNK_ROWS) * N * 4;
+    return R <= BN_SMALL_R ? 0 : (long long)bn_chunks(R) * N * 4;
 }
 extern "C" int dir_colsum_f32(const float* x, float* out, int R, int N, int ld, int accumulate, float* workspace, long long workspace_bytes, void* stream) {
     using namespace dir;
@@ -1866,7 +1691,7 @@ extern "C" int dir_colsum_f32(const float* x, float* out, int R, int N, int ld, 
     }
     // tall matrices (bias gradients of the convolutions: R = B*Ho*Wo): 256-row chunk partials, added in chunk order
     DIR_REQUIRE(workspace && workspace_bytes >= dir_colsum_workspace_bytes(R, N), "dir_colsum_f32: workspace too small (dir_colsum_workspace_bytes)");
-    const int chunks = (R + BN_CHUNK_ROWS - 1) / BN_CHUNK_ROWS;
+    const int chunks = bn_chunks(R);
     launch_bn_partial(dim3((N + 63) / 64, chunks), s, x, nullptr, nullptr, nullptr, workspace, nullptr, R, N, ld, 0);
     if (accumulate) DIR_LAUNCH(wgrad_reduce_kernel, dim3((N + 255) / 256), dim3(256), 0, s, (const float*)workspace, out, (long long)N, chunks, accumulate);
     else DIR_LAUNCH(bn_colsum_chunks_kernel, dim3((N + 15) / 16), dim3(256), 0, s, (const float*)workspace, out, chunks, N, 1.f);
@@ -1919,80 +1744,12 @@ extern "C" int dir_attention_backward(const float* qkv, const float* probs, cons
 
 extern "C" long long dir_bn_train_workspace_bytes(int R, int C) {
     if (R <= 0 || C <= 0) return -1;
-    if (R <= BN_SMALL_R) return 0;
-    const long long chunks = (R + BN_CHUNK_ROWS - 1) / BN_CHUNK_ROWS;
-    return (2 * chunks + 2) * C * 4;
+    return R <= BN_SMALL_R ? 0 : bn_plan(R, C).end * 4;
 }
 static bool bn_vec4(int C, int ld, std::initializer_list<const void*> ps) {
     if (C % 4 || ld % 4) return false;
     for (const void* q : ps) if (q && ((uintptr_t)q & 15)) return false;
     return true;
-}
-// ---- one-launch BatchNorm: the library-owned sync words (one block per stream that ever ran a BatchNorm, from a pool allocated and zeroed at the
-// first call -- never inside a stream capture: a stream first seen while capturing takes a block of the pool, and with the pool absent or spent
-// the three-launch path runs) and the persistent grid's size
-constexpr int BN_ONE_POOL = 16, BN_ONE_DEVICES = 16;
-struct BnOnePool { int* base = nullptr; int used = 0; hipStream_t streams[BN_ONE_POOL]; };
-static std::mutex bn_one_mu;
-static int bn_one_switch = -1;           // -1: not read yet (DIR_BN_ONE_LAUNCH, default OFF: measured slower, below) | 0 | 1; dir_bn_one_launch_enable sets it
-static bool bn_one_enabled() {
-    std::lock_guard<std::mutex> lock(bn_one_mu);
-    if (bn_one_switch < 0) { const char* e = getenv("DIR_BN_ONE_LAUNCH"); bn_one_switch = e && e[0] == '1'; }
-    return bn_one_switch != 0;
-}
-static BnOnePool bn_one_pools[BN_ONE_DEVICES];
-static int* bn_one_words(hipStream_t s) {
-    if (!bn_one_enabled()) return nullptr;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= BN_ONE_DEVICES) return nullptr;
-    std::lock_guard<std::mutex> lock(bn_one_mu);
-    BnOnePool& p = bn_one_pools[dev];
-    if (!p.base) {
-        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(s, &st) != hipSuccess || st != hipStreamCaptureStatusNone) return nullptr;
-        int* q = nullptr;
-        if (hipMalloc(&q, sizeof(int) * BN_ONE_WORDS * BN_ONE_POOL) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        if (hipMemset(q, 0, sizeof(int) * BN_ONE_WORDS * BN_ONE_POOL) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(q); return nullptr; }
-        p.base = q;
-    }
-    for (int i = 0; i < p.used; ++i) if (p.streams[i] == s) return p.base + (long long)i * BN_ONE_WORDS;
-    if (p.used == BN_ONE_POOL) return nullptr;
-    p.streams[p.used] = s;
-    return p.base + (long long)(p.used++) * BN_ONE_WORDS;
-}
-template <typename K>
-static int bn_one_grid(K kernel, int ntile) {
-    static const int slots = [kernel]() {
-        int dev = 0, cus = 256, occ = 4;
-        if (hipGetDevice(&dev) == hipSuccess) {
-            hipDeviceProp_t pr;
-            if (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) cus = pr.multiProcessorCount;
-        }
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, 256, 0) != hipSuccess || occ < 1) occ = 1;
-        return cus * (occ > 1 ? occ * 3 / 4 : 1);          // every workgroup of the launch must be resident at once (they wait on each other): below what fits
-    }();
-    return ntile < slots ? ntile : slots;
-}
-// 0, or 1 if a workgroup of a one-launch BatchNorm on the current device ever gave up waiting (that launch's outputs were wrong); the sync words
-// of the device are cleared.  Synchronises the device: nothing in the training step calls this -- tests and the eager (calibration) steps do.
-extern "C" int dir_bn_one_launch_enable(int on) {
-    const bool was = bn_one_enabled();
-    std::lock_guard<std::mutex> lock(bn_one_mu);
-    bn_one_switch = on != 0;
-    return was;
-}
-extern "C" int dir_bn_one_launch_status(void) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= BN_ONE_DEVICES) return 0;
-    std::lock_guard<std::mutex> lock(bn_one_mu);
-    BnOnePool& p = bn_one_pools[dev];
-    if (!p.base) return 0;
-    static int host[BN_ONE_WORDS * BN_ONE_POOL];
-    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(host, p.base, sizeof(host), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    int bad = 0;
-    for (int i = 0; i < BN_ONE_POOL; ++i) bad |= host[i * BN_ONE_WORDS + 3 * BN_ONE_GROUPS] != 0;
-    if (bad && hipMemset(p.base, 0, sizeof(host)) != hipSuccess) return -1;
-    return bad;
 }
 extern "C" int dir_bn_train_forward(const float* x, const float* w, const float* b, float* y, float* save_mean, float* save_rstd, float* running_mean,
                                     float* running_var, int R, int C, int ld, float eps, float momentum, int relu, const float* residual,
@@ -2010,32 +1767,21 @@ extern "C" int dir_bn_train_forward(const float* x, const float* w, const float*
         return check_launch("dir_bn_train_forward");
     }
     DIR_REQUIRE(workspace && workspace_bytes >= dir_bn_train_workspace_bytes(R, C), "dir_bn_train_forward: workspace too small (dir_bn_train_workspace_bytes)");
-    const int chunks = (R + BN_CHUNK_ROWS - 1) / BN_CHUNK_ROWS;
+    const BnPlan pl = bn_plan(R, C);
+    const int chunks = pl.chunks;
     float* part = workspace;
-    const dim3 pg((C + 63) / 64, chunks), cg((C + 15) / 16);
-    if (bn_vec4(C, ld, {x, y, w, b, save_mean, save_rstd, workspace, residual})) {
-        float* p2 = part + (long long)chunks * C;
-        int* words = (int)pg.x <= BN_ONE_GROUPS ? bn_one_words(s) : nullptr;
-        if (words) {
-            BnOne a{};
-            a.x = x; a.w = w; a.b = b; a.res = residual; a.y = y; a.save_mean = save_mean; a.save_rstd = save_rstd; a.running_mean = running_mean;
-            a.running_var = running_var; a.p1 = part; a.p2 = p2; a.words = words; a.R = R; a.C = C; a.ld = ld; a.relu = relu; a.chunks = chunks;
-            a.cgroups = (int)pg.x; a.eps = eps; a.momentum = momentum;
-            DIR_LAUNCH(bn_one_fwd_kernel, dim3(bn_one_grid(bn_one_fwd_kernel, a.cgroups * chunks)), dim3(256), 0, s, a);
-            return check_launch("dir_bn_train_forward");
-        }
-        DIR_LAUNCH(bn_stats4_kernel, pg, dim3(256), 0, s, x, part, p2, R, C, ld);
-        DIR_LAUNCH(bn_stats_combine_kernel, cg, dim3(256), 0, s, (const float*)part, (const float*)p2, save_mean, save_rstd, running_mean, running_var, chunks, R, C, eps, momentum);
-        const long long nt = (long long)((R + 3) / 4) * (C / 4);
-        DIR_LAUNCH(bn_apply_fwd4_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, x, w, b, (const float*)save_mean, (const float*)save_rstd, y, R, C, ld, relu, residual);
-        return check_launch("dir_bn_train_forward");
+    const bool vec = bn_vec4(C, ld, {x, y, w, b, save_mean, save_rstd, workspace, residual});
+    if (vec) {
+        float* p2 = part + pl.p2;
+        DIR_LAUNCH(bn_stats4_kernel, pl.pg, dim3(256), 0, s, x, part, p2, R, C, ld);
+        DIR_LAUNCH(bn_stats_combine_kernel, pl.cg, dim3(256), 0, s, (const float*)part, (const float*)p2, save_mean, save_rstd, running_mean, running_var, chunks, R, C, eps, momentum);
+    } else {
+        launch_bn_partial(pl.pg, s, x, nullptr, nullptr, nullptr, part, nullptr, R, C, ld, 0);
+        DIR_LAUNCH(bn_colsum_chunks_kernel, pl.cg, dim3(256), 0, s, (const float*)part, save_mean, chunks, C, 1.f / R);
+        launch_bn_partial(pl.pg, s, x, nullptr, save_mean, nullptr, part, nullptr, R, C, ld, 1);
+        DIR_LAUNCH(bn_stats_finalize_kernel, pl.cg, dim3(256), 0, s, (const float*)part, (const float*)save_mean, save_mean, save_rstd, running_mean, running_var, chunks, R, C, eps, momentum);
     }
-    launch_bn_partial(pg, s, x, nullptr, nullptr, nullptr, part, nullptr, R, C, ld, 0);
-    DIR_LAUNCH(bn_colsum_chunks_kernel, cg, dim3(256), 0, s, (const float*)part, save_mean, chunks, C, 1.f / R);
-    launch_bn_partial(pg, s, x, nullptr, save_mean, nullptr, part, nullptr, R, C, ld, 1);
-    DIR_LAUNCH(bn_stats_finalize_kernel, cg, dim3(256), 0, s, (const float*)part, (const float*)save_mean, save_mean, save_rstd, running_mean, running_var, chunks, R, C, eps, momentum);
-    const long long n = (long long)R * C;
-    DIR_LAUNCH(bn_apply_fwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, w, b, (const float*)save_mean, (const float*)save_rstd, y, n, C, ld, relu, residual);
+    launch_bn_apply_fwd(s, vec, x, w, b, save_mean, save_rstd, y, R, C, ld, relu, residual);
     return check_launch("dir_bn_train_forward");
 }
 extern "C" int dir_bn_train_stats(const float* x, const float* w, const float* b, float* save_mean, float* save_rstd, float* pre_scale, float* pre_shift,
@@ -2047,12 +1793,11 @@ extern "C" int dir_bn_train_stats(const float* x, const float* w, const float* b
     DIR_REQUIRE(bn_vec4(C, ld, {x, w, b, save_mean, save_rstd, workspace}), "dir_bn_train_stats: C and ld must be multiples of 4, pointers 16-byte aligned");
     DIR_REQUIRE(workspace && workspace_bytes >= dir_bn_train_workspace_bytes(R, C), "dir_bn_train_stats: workspace too small (dir_bn_train_workspace_bytes)");
     hipStream_t s = (hipStream_t)stream;
-    const int chunks = (R + BN_CHUNK_ROWS - 1) / BN_CHUNK_ROWS;
-    float* part = workspace; float* p2 = part + (long long)chunks * C;
-    const dim3 pg((C + 63) / 64, chunks), cg((C + 15) / 16);
-    DIR_LAUNCH(bn_stats4_kernel, pg, dim3(256), 0, s, x, part, p2, R, C, ld);
-    DIR_LAUNCH(bn_stats_combine_pre_kernel, cg, dim3(256), 0, s, (const float*)part, (const float*)p2, w, b, save_mean, save_rstd, pre_scale, pre_shift, running_mean,
-               running_var, chunks, R, C, eps, momentum, BN_CHUNK_ROWS);
+    const BnPlan pl = bn_plan(R, C);
+    float* part = workspace; float* p2 = part + pl.p2;
+    DIR_LAUNCH(bn_stats4_kernel, pl.pg, dim3(256), 0, s, x, part, p2, R, C, ld);
+    DIR_LAUNCH(bn_stats_combine_pre_kernel, pl.cg, dim3(256), 0, s, (const float*)part, (const float*)p2, w, b, save_mean, save_rstd, pre_scale, pre_shift, running_mean,
+               running_var, pl.chunks, R, C, eps, momentum, BN_CHUNK_ROWS);
     return check_launch("dir_bn_train_stats");
 }
 // Chunk partials -> partials of GROUPS of `per` consecutive chunks (same meaning: column sum | sum of squared deviations from the group's own mean),
@@ -2116,8 +1861,7 @@ extern "C" int dir_bn_train_apply(const float* x, const float* w, const float* b
     using namespace dir;
     DIR_REQUIRE(x && y && save_mean && save_rstd && R > 0 && C > 0 && ld >= C, "dir_bn_train_apply: bad arguments");
     DIR_REQUIRE(bn_vec4(C, ld, {x, y, w, b, save_mean, save_rstd, residual}), "dir_bn_train_apply: C and ld must be multiples of 4, pointers 16-byte aligned");
-    const long long nt = (long long)((R + 3) / 4) * (C / 4);
-    DIR_LAUNCH(bn_apply_fwd4_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, w, b, save_mean, save_rstd, y, R, C, ld, relu, residual);
+    launch_bn_apply_fwd((hipStream_t)stream, true, x, w, b, save_mean, save_rstd, y, R, C, ld, relu, residual);
     return check_launch("dir_bn_train_apply");
 }
 // both in one call: statistics from the producing convolution's chunk partials, then y = act(BatchNorm(x) + residual)
@@ -2143,31 +1887,12 @@ extern "C" int dir_bn_train_backward(const float* gy, const float* x, const floa
         return check_launch("dir_bn_train_backward");
     }
     DIR_REQUIRE(workspace && workspace_bytes >= dir_bn_train_workspace_bytes(R, C), "dir_bn_train_backward: workspace too small (dir_bn_train_workspace_bytes)");
-    const int chunks = (R + BN_CHUNK_ROWS - 1) / BN_CHUNK_ROWS;
-    float* p1 = workspace; float* p2 = p1 + (long long)chunks * C; float* t1 = p2 + (long long)chunks * C; float* t2 = t1 + C;
-    const dim3 pg((C + 63) / 64, chunks), cg((C + 15) / 16);
+    const BnPlan pl = bn_plan(R, C);
+    float* p1 = workspace; float* p2 = p1 + pl.p2; float* t1 = p1 + pl.t1; float* t2 = p1 + pl.t2;
     const bool vec = bn_vec4(C, ld, {x, gy, gx, w, b, save_mean, save_rstd, workspace});
-    int* words = vec && (int)pg.x <= BN_ONE_GROUPS ? bn_one_words(s) : nullptr;
-    if (words) {
-        BnOne a{};
-        a.x = x; a.gy = gy; a.w = w; a.b = b; a.gx = gx; a.save_mean = const_cast<float*>(save_mean); a.save_rstd = const_cast<float*>(save_rstd);
-        a.gw = gw; a.gb = gb; a.p1 = p1; a.p2 = p2; a.t1 = t1; a.t2 = t2; a.words = words; a.R = R; a.C = C; a.ld = ld; a.relu = relu; a.chunks = chunks;
-        a.cgroups = (int)pg.x;
-        DIR_LAUNCH(bn_one_bwd_kernel, dim3(bn_one_grid(bn_one_bwd_kernel, a.cgroups * chunks)), dim3(256), 0, s, a);
-        return check_launch("dir_bn_train_backward");
-    }
-    if (vec) DIR_LAUNCH(bn_bwd_partial4_kernel, pg, dim3(256), 0, s, x, gy, w, b, save_mean, save_rstd, p1, p2, R, C, ld, relu);
-    else launch_bn_partial(pg, s, x, gy, save_mean, save_rstd, p1, p2, R, C, ld, 2, w, b, relu);
-    DIR_LAUNCH(bn_bwd_combine_kernel, cg, dim3(256), 0, s, (const float*)p1, (const float*)p2, t1, t2, gb, gw, chunks, C);
-    if (gx) {
-        if (vec) {
-            const long long nt = (long long)((R + 3) / 4) * (C / 4);
-            DIR_LAUNCH(bn_apply_bwd4_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, gy, x, w, b, save_mean, save_rstd, (const float*)t1, (const float*)t2, gx, R, C, ld, relu);
-        } else {
-            const long long n = (long long)R * C;
-            DIR_LAUNCH(bn_apply_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, gy, x, w, b, save_mean, save_rstd, (const float*)t1, (const float*)t2, gx, n, R, C, ld, relu);
-        }
-    }
+    launch_bn_bwd_partial(s, vec, pl.pg, x, gy, w, b, save_mean, save_rstd, p1, p2, R, C, ld, relu);
+    DIR_LAUNCH(bn_bwd_combine_kernel, pl.cg, dim3(256), 0, s, (const float*)p1, (const float*)p2, t1, t2, gb, gw, pl.chunks, C);
+    if (gx) launch_bn_apply_bwd(s, vec, gy, x, w, b, save_mean, save_rstd, t1, t2, gx, R, C, ld, relu);
     return check_launch("dir_bn_train_backward");
 }
 
@@ -2181,18 +1906,14 @@ extern "C" int dir_bn_train_backward_from_partials(const float* gy, const float*
     hipStream_t s = (hipStream_t)stream;
     float* t1 = workspace; float* t2 = t1 + C;
     DIR_LAUNCH(bn_bwd_combine_kernel, dim3((C + 15) / 16), dim3(256), 0, s, p1, p2, t1, t2, gb, gw, chunks, C);
-    if (gx) {
-        const long long nt = (long long)((R + 3) / 4) * (C / 4);
-        DIR_LAUNCH(bn_apply_bwd4_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, gy, x, w, b, save_mean, save_rstd, (const float*)t1, (const float*)t2, gx, R, C, ld, relu);
-    }
+    if (gx) launch_bn_apply_bwd(s, true, gy, x, w, b, save_mean, save_rstd, t1, t2, gx, R, C, ld, relu);
     return check_launch("dir_bn_train_backward_from_partials");
 }
 
 // ---- SyncBN building blocks (dir_amd/train/ops.py: sync_bn_fwd / sync_bn_bwd put the collectives between them)
 extern "C" long long dir_bn_sync_workspace_bytes(int R, int C) {
     if (R <= 0 || C <= 0) return -1;
-    const long long chunks = (R + BN_CHUNK_ROWS - 1) / BN_CHUNK_ROWS;
-    return 2 * chunks * C * 4;
+    return bn_plan(R, C).t1 * 4;
 }
 extern "C" int dir_bn_sync_local_stats(const float* x, float* part, int R, int C, int ld, float* workspace, long long workspace_bytes, void* stream) {
     using namespace dir;
@@ -2200,10 +1921,10 @@ extern "C" int dir_bn_sync_local_stats(const float* x, float* part, int R, int C
     DIR_REQUIRE(bn_vec4(C, ld, {x, part, workspace}), "dir_bn_sync_local_stats: C and ld must be multiples of 4, pointers 16-byte aligned");
     DIR_REQUIRE(workspace && workspace_bytes >= dir_bn_sync_workspace_bytes(R, C), "dir_bn_sync_local_stats: workspace too small (dir_bn_sync_workspace_bytes)");
     hipStream_t s = (hipStream_t)stream;
-    const int chunks = (R + BN_CHUNK_ROWS - 1) / BN_CHUNK_ROWS;
-    float* p1 = workspace; float* p2 = p1 + (long long)chunks * C;
-    DIR_LAUNCH(bn_stats4_kernel, dim3((C + 63) / 64, chunks), dim3(256), 0, s, x, p1, p2, R, C, ld);
-    DIR_LAUNCH(bn_stats_local_kernel, dim3((C + 15) / 16), dim3(256), 0, s, (const float*)p1, (const float*)p2, part, part + C, chunks, R, C);
+    const BnPlan pl = bn_plan(R, C);
+    float* p1 = workspace; float* p2 = p1 + pl.p2;
+    DIR_LAUNCH(bn_stats4_kernel, pl.pg, dim3(256), 0, s, x, p1, p2, R, C, ld);
+    DIR_LAUNCH(bn_stats_local_kernel, pl.cg, dim3(256), 0, s, (const float*)p1, (const float*)p2, part, part + C, pl.chunks, R, C);
     return check_launch("dir_bn_sync_local_stats");
 }
 extern "C" int dir_bn_sync_combine(const float* parts, int world, int C, float* mean, float* var, float* running_mean, float* running_var, float momentum,
@@ -2220,10 +1941,10 @@ extern "C" int dir_bn_sync_backward_sums(const float* gy, const float* x, const 
     DIR_REQUIRE(bn_vec4(C, ld, {x, gy, w, b, save_mean, save_rstd, sums, workspace}), "dir_bn_sync_backward_sums: C and ld must be multiples of 4, pointers 16-byte aligned");
     DIR_REQUIRE(workspace && workspace_bytes >= dir_bn_sync_workspace_bytes(R, C), "dir_bn_sync_backward_sums: workspace too small (dir_bn_sync_workspace_bytes)");
     hipStream_t s = (hipStream_t)stream;
-    const int chunks = (R + BN_CHUNK_ROWS - 1) / BN_CHUNK_ROWS;
-    float* p1 = workspace; float* p2 = p1 + (long long)chunks * C;
-    DIR_LAUNCH(bn_bwd_partial4_kernel, dim3((C + 63) / 64, chunks), dim3(256), 0, s, x, gy, w, b, save_mean, save_rstd, p1, p2, R, C, ld, relu);
-    DIR_LAUNCH(bn_bwd_sums_kernel, dim3((C + 15) / 16), dim3(256), 0, s, (const float*)p1, (const float*)p2, sums, chunks, C);
+    const BnPlan pl = bn_plan(R, C);
+    float* p1 = workspace; float* p2 = p1 + pl.p2;
+    launch_bn_bwd_partial(s, true, pl.pg, x, gy, w, b, save_mean, save_rstd, p1, p2, R, C, ld, relu);
+    DIR_LAUNCH(bn_bwd_sums_kernel, pl.cg, dim3(256), 0, s, (const float*)p1, (const float*)p2, sums, pl.chunks, C);
     return check_launch("dir_bn_sync_backward_sums");
 }
 extern "C" int dir_bn_sync_backward_apply(const float* gy, const float* x, const float* w, const float* b, const float* save_mean, const float* save_rstd,
@@ -2231,9 +1952,7 @@ extern "C" int dir_bn_sync_backward_apply(const float* gy, const float* x, const
     using namespace dir;
     DIR_REQUIRE(gy && x && save_mean && save_rstd && sums_pooled && gx && R > 0 && C > 0 && ld >= C && rows_pooled >= (float)R, "dir_bn_sync_backward_apply: bad arguments");
     DIR_REQUIRE(bn_vec4(C, ld, {x, gy, gx, w, b, save_mean, save_rstd, sums_pooled}), "dir_bn_sync_backward_apply: C and ld must be multiples of 4, pointers 16-byte aligned");
-    const long long nt = (long long)((R + 3) / 4) * (C / 4);
-    DIR_LAUNCH(bn_apply_bwd4_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, (hipStream_t)stream, gy, x, w, b, save_mean, save_rstd, sums_pooled,
-               sums_pooled + C, gx, R, C, ld, relu, rows_pooled);
+    launch_bn_apply_bwd((hipStream_t)stream, true, gy, x, w, b, save_mean, save_rstd, sums_pooled, sums_pooled + C, gx, R, C, ld, relu, rows_pooled);
     return check_launch("dir_bn_sync_backward_apply");
 }
 
@@ -2243,8 +1962,7 @@ extern "C" int dir_bn_sync_backward_apply(const float* gy, const float* x, const
 // training-mode backward), g x = gy w rstd (no batch-statistics terms).  save_mean / save_rstd are written by the forward for the backward.
 extern "C" long long dir_bn_frozen_workspace_bytes(int R, int C) {
     if (R <= 0 || C <= 0) return -1;
-    const long long chunks = (R + BN_CHUNK_ROWS - 1) / BN_CHUNK_ROWS;
-    return (2 * chunks + 2) * C * 4;
+    return bn_plan(R, C).end * 4;
 }
 extern "C" int dir_bn_frozen_forward(const float* x, const float* w, const float* b, float* y, float* save_mean, float* save_rstd, const float* running_mean,
                                      const float* running_var, int R, int C, int ld, float eps, int relu, const float* residual, void* stream) {
@@ -2252,13 +1970,7 @@ extern "C" int dir_bn_frozen_forward(const float* x, const float* w, const float
     DIR_REQUIRE(x && y && save_mean && save_rstd && running_mean && running_var && R > 0 && C > 0 && ld >= C, "dir_bn_frozen_forward: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     DIR_LAUNCH(bn_frozen_stats_kernel, dim3((C + 255) / 256), dim3(256), 0, s, running_mean, running_var, save_mean, save_rstd, C, eps);
-    if (bn_vec4(C, ld, {x, y, w, b, save_mean, save_rstd, residual})) {
-        const long long nt = (long long)((R + 3) / 4) * (C / 4);
-        DIR_LAUNCH(bn_apply_fwd4_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, x, w, b, (const float*)save_mean, (const float*)save_rstd, y, R, C, ld, relu, residual);
-    } else {
-        const long long n = (long long)R * C;
-        DIR_LAUNCH(bn_apply_fwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x, w, b, (const float*)save_mean, (const float*)save_rstd, y, n, C, ld, relu, residual);
-    }
+    launch_bn_apply_fwd(s, bn_vec4(C, ld, {x, y, w, b, save_mean, save_rstd, residual}), x, w, b, save_mean, save_rstd, y, R, C, ld, relu, residual);
     return check_launch("dir_bn_frozen_forward");
 }
 extern "C" int dir_bn_frozen_backward(const float* gy, const float* x, const float* w, const float* b, const float* save_mean, const float* save_rstd, float* gx,
@@ -2267,22 +1979,14 @@ extern "C" int dir_bn_frozen_backward(const float* gy, const float* x, const flo
     DIR_REQUIRE(gy && x && save_mean && save_rstd && R > 0 && C > 0 && ld >= C, "dir_bn_frozen_backward: bad arguments");
     DIR_REQUIRE(workspace && workspace_bytes >= dir_bn_frozen_workspace_bytes(R, C), "dir_bn_frozen_backward: workspace too small (dir_bn_frozen_workspace_bytes)");
     hipStream_t s = (hipStream_t)stream;
-    const int chunks = (R + BN_CHUNK_ROWS - 1) / BN_CHUNK_ROWS;
-    float* p1 = workspace; float* p2 = p1 + (long long)chunks * C; float* t1 = p2 + (long long)chunks * C; float* t2 = t1 + C;
-    const dim3 pg((C + 63) / 64, chunks), cg((C + 15) / 16);
+    const BnPlan pl = bn_plan(R, C);
+    float* p1 = workspace; float* p2 = p1 + pl.p2; float* t1 = p1 + pl.t1; float* t2 = p1 + pl.t2;
     const bool vec = bn_vec4(C, ld, {x, gy, gx, w, b, save_mean, save_rstd, workspace});
-    if (vec) DIR_LAUNCH(bn_bwd_partial4_kernel, pg, dim3(256), 0, s, x, gy, w, b, save_mean, save_rstd, p1, p2, R, C, ld, relu);
-    else launch_bn_partial(pg, s, x, gy, save_mean, save_rstd, p1, p2, R, C, ld, 2, w, b, relu);
-    DIR_LAUNCH(bn_bwd_combine_kernel, cg, dim3(256), 0, s, (const float*)p1, (const float*)p2, t1, t2, gb, gw, chunks, C);
+    launch_bn_bwd_partial(s, vec, pl.pg, x, gy, w, b, save_mean, save_rstd, p1, p2, R, C, ld, relu);
+    DIR_LAUNCH(bn_bwd_combine_kernel, pl.cg, dim3(256), 0, s, (const float*)p1, (const float*)p2, t1, t2, gb, gw, pl.chunks, C);
     if (gx) {
         DIR_LAUNCH(zero_f32_kernel, dim3((2 * C + 255) / 256), dim3(256), 0, s, t1, 2 * C);          // no batch-statistics terms: the apply kernels' column means are zero
-        if (vec) {
-            const long long nt = (long long)((R + 3) / 4) * (C / 4);
-            DIR_LAUNCH(bn_apply_bwd4_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, s, gy, x, w, b, save_mean, save_rstd, (const float*)t1, (const float*)t2, gx, R, C, ld, relu);
-        } else {
-            const long long n = (long long)R * C;
-            DIR_LAUNCH(bn_apply_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, gy, x, w, b, save_mean, save_rstd, (const float*)t1, (const float*)t2, gx, n, R, C, ld, relu);
-        }
+        launch_bn_apply_bwd(s, vec, gy, x, w, b, save_mean, save_rstd, t1, t2, gx, R, C, ld, relu);
     }
     return check_launch("dir_bn_frozen_backward");
 }

@@ -1140,7 +1140,6 @@ class DirEngine(object):
         self.dtype, self.device = dtype, torch.device(device)
         sd = {k: v.detach().to(self.device) for k, v in state_dict.items()}
         self.keep = []
-        self._pgcn_ws = {}
         _TLS.arith = arith
         try:
             self._pack(sd, root_joint)
@@ -1258,12 +1257,8 @@ class DirEngine(object):
         wes = 2 if self.dtype in HALF else 4
         _ann('pgcn', 2.0 * 4 * 2 * B * 21 * 2 * 128 * 128, 4 * 2 * (2 * 21 * 128 * 128 * wes + 2 * B * 21 * 128 * 4),
              'B=%d 4 layers x 2 hands (per-node W0/W1 %s + neighbour mix + BN + ReLU)' % (B, 'bf16' if wes == 2 else 'f32'))
-        if self.pgcn_fused:      # the whole stack of both hands in one launch, layers separated by per-node flags (tokens.hip: pgcn_fused_kernel)
-            _capi.check(L.dir_pgcn_stack_forward_fused(st.gcn[0], st.gcn[1], 4, _capi.ptr(x0), _capi.ptr(gp), _capi.ptr(tok), _capi.ptr(scratch),
-                                                       _capi.ptr(self._pgcn_sync()), 0, B, sp), 'dir_pgcn_stack_forward_fused')
-        else:
-            _capi.check(L.dir_pgcn_stack_forward_pair(st.gcn[0], st.gcn[1], 4, _capi.ptr(x0), _capi.ptr(gp), _capi.ptr(tok),
-                                                      _capi.ptr(scratch), B, sp), 'dir_pgcn_stack_forward_pair')
+        _capi.check(L.dir_pgcn_stack_forward_pair(st.gcn[0], st.gcn[1], 4, _capi.ptr(x0), _capi.ptr(gp), _capi.ptr(tok),
+                                                  _capi.ptr(scratch), B, sp), 'dir_pgcn_stack_forward_pair')
         y = torch.empty(B, 42, 64, device=dev, dtype=F32)
         blk = 42 * 128 * 384 + 4 * 2 * 42 * 42 * 32 + 42 * 128 * 128 + 2 * 42 * 128 * 256
         _ann('ste', 2.0 * B * (3 * blk + 42 * 128 * 64), B * 42 * (128 + 64) * 4 + (3 * (128 * 384 + 128 * 128 + 2 * 128 * 256) + 128 * 64) * wes,
@@ -1323,27 +1318,6 @@ class DirEngine(object):
         res['joint_feat'] = emb
         res['vis_img_feat'] = vis
         return res
-
-    # The P-GCN stack of both hands as ONE launch (tokens.hip: pgcn_fused_kernel, layers separated by per-node flags): built, bit-identical, and
-    # measured no faster than the five launches it replaces (B = 64: 29.9 us with 4 splits against 31.4 us; 38 us with the 2 splits that keep six
-    # concurrent launches co-resident) -- a device-coherent hand-off costs what a kernel boundary costs.  Off unless DIR_PGCN_FUSED=1.
-    pgcn_fused = os.environ.get('DIR_PGCN_FUSED', '0') == '1'
-
-    def _pgcn_sync(self):
-        """the fused P-GCN launch's flag words: zeroed once, one buffer per stream that runs forwards of this engine (two streams' launches must
-        not share flags); never reset afterwards -- every launch raises its flags by one (tokens.hip).  Allocated outside any capture when the
-        stream has run an eager forward first (ForwardPipeline does); allocated inside a capture it is re-zeroed by every replay, which is
-        equally correct."""
-        key = torch.cuda.current_stream(self.device).cuda_stream
-        ws = self._pgcn_ws.get(key)
-        if ws is None:
-            ws = torch.zeros(int(_capi.lib().dir_pgcn_fused_sync_bytes()) // 4, dtype=torch.int32, device=self.device)
-            self._pgcn_ws[key] = ws
-        return ws
-
-    def pgcn_sync_error(self):
-        """True if a fused P-GCN workgroup of any stream ever gave up waiting for a neighbour (host read; tests and bench.py look)"""
-        return any(int(ws[-4].item()) != 0 for ws in self._pgcn_ws.values())
 
     def _stage_index(self, st):
         """position of the stage's dict in outs_list (0 = the init regression)"""

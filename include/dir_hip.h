@@ -29,7 +29,7 @@ extern "C" {
 #define DIR_E_LAUNCH (-2)   /* hipLaunchKernel / HIP runtime error          */
 #define DIR_E_NODEVICE (-3) /* no gfx950 device visible                     */
 
-#define DIR_ABI_VERSION 48
+#define DIR_ABI_VERSION 49
 
 int dir_abi_version(void);
 const char* dir_last_error(void);
@@ -185,18 +185,8 @@ int dir_attention_backward(const float* qkv, const float* probs, const float* go
  * (models/backbone/resnet.py:136-140); the backward of THAT form masks with the saved output instead (dir_relu_backward) and passes relu = 0.  R <= 512: one
  * thread per channel walks the rows in order, no workspace.  Larger R (BatchNorm2d over feature maps): the column reductions are cut
  * into 256-row chunks whose partials are combined in chunk order (deterministic; the variance as sum_k [M2_k + n_k (mean_k - mean)^2] / R,
- * one pass over HBM); workspace of dir_bn_train_workspace_bytes(R, C).
- * R > 512, C % 4 == 0 (round 5), OPTIONAL: one launch each way instead of three -- a persistent grid (every workgroup resident) walks the same
- * chunks; the workgroup whose chunk reaches a 64-channel group's counter last combines that group's partials (in chunk order: the same bits as
- * the three launches), the others wait on the group's flag and then normalise the chunks they read.  The counters live in library-owned device
- * words, one block per stream (allocated at the first call outside a stream capture; no block -> the three launches run), and are left zero by
- * every launch.  A workgroup that waits longer than 4 s gives up and raises the error word dir_bn_one_launch_status() reports (0 | 1; it
- * synchronises the device and clears the words; the step never calls it).  OFF by default: measured 3 % slower per training step than the three
- * launches at 32 images (profiles/r05_bn_one_launch_ab.txt); DIR_BN_ONE_LAUNCH=1 in the environment or dir_bn_one_launch_enable(1) (returns the
- * previous setting) turns it on. */
+ * one pass over HBM); workspace of dir_bn_train_workspace_bytes(R, C). */
 long long dir_bn_train_workspace_bytes(int R, int C);
-int dir_bn_one_launch_status(void);
-int dir_bn_one_launch_enable(int on);
 int dir_bn_train_forward(const float* x, const float* w, const float* b, float* y, float* save_mean, float* save_rstd, float* running_mean,
                          float* running_var, int R, int C, int ld, float eps, float momentum, int relu, const float* residual,
                          float* workspace, long long workspace_bytes, void* stream);
@@ -680,17 +670,6 @@ int dir_pgcn_stack_forward(const dir_pgcn_layer* layers_host, int num_layers, co
 int dir_pgcn_stack_forward_pair(const dir_pgcn_layer* layers_left_host, const dir_pgcn_layer* layers_right_host,
                                 int num_layers, const float* x_lr, const float* add_lr, float* tokens, float* scratch,
                                 int B, void* stream);
-
-/* The same stack of both hands in ONE launch (round 4; replaces the five launches of dir_pgcn_stack_forward_pair, same arithmetic, bit-identical
- * tokens): one persistent workgroup per (hand, node, batch split) runs all layers of its node; layers are separated by per-node flags in
- * `sync_ws` (device memory, dir_pgcn_fused_sync_bytes() bytes, ZEROED ONCE by the caller and then left alone -- every launch raises the flags it
- * owns by one; one sync_ws per stream that may run this concurrently) instead of launches.  splits: batch splits per node (0 = the library's
- * choice; <= 8; DIR_PGCN_SPLITS overrides).  The word at byte offset dir_pgcn_fused_sync_bytes() - 16 becomes nonzero if a workgroup ever gave up
- * waiting (~1 s) for a neighbour -- the tokens of that launch are then invalid.  num_layers <= 4.  scratch as for the pair entry point. */
-long long dir_pgcn_fused_sync_bytes(void);
-int dir_pgcn_stack_forward_fused(const dir_pgcn_layer* layers_left_host, const dir_pgcn_layer* layers_right_host, int num_layers,
-                                 const float* x_lr, const float* add_lr, float* tokens, float* scratch, void* sync_ws, int splits, int B,
-                                 void* stream);
 
 /* a6: STE.forward (transformer/mixSTE.py:194-205) on [B,42,128] -> [B,42,64].
  * weight_dtype DIR_DT_F32: the six Linear weights per block (*_wt) and head_wt are fp32, k-major ([in][out]); exact fp32.

@@ -8,7 +8,7 @@ float64 references, S and the check: tests/helpers/norm_cases.py, proved on the 
  3. every case runs a second time -- through dir_amd.train.ops where the case is contiguous and aligned -- and must give the same bits;
  4. where include/dir_hip.h promises the same bits they are asserted: dir_bn_train_stats (+ dir_bn_train_apply) against dir_bn_train_forward,
     dir_bn_train_stats_from_partials against dir_bn_train_forward_from_partials, attention with save_probs off against on.
-The one-launch BatchNorm stays off (its default); SyncBN's building blocks run in ONE process on row splits of one batch, no collectives.
+SyncBN's building blocks run in ONE process on row splits of one batch, no collectives.
 
 The constants c are NOT measured here: each is 4 x the larger error of two float32 CPU references (norm_cases.RATIOS), capped per case at the
 serial bound (chain + 4).  For information, the kernels' own largest ratios on the MI355X, in units of 2^-24 S (NORM-CLASS lines of a -s run):
