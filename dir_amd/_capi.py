@@ -136,12 +136,18 @@ class OneEuroSegment(C.Structure):       # dir_one_euro_segment
     _fields_ = [('n_points', C.c_int32), ('dims', C.c_int32), ('speed_scale', C.c_float)]
 
 
+class GuardState(C.Structure):           # dir_guard_state
+    _fields_ = [('sumsq', C.c_double), ('norm', C.c_double), ('bc1', C.c_double), ('applied', C.c_longlong), ('skipped', C.c_longlong),
+                ('skipped_in_row', C.c_longlong), ('clipped', C.c_longlong), ('coef', C.c_float), ('bc2_sqrt', C.c_float),
+                ('nonfinite', C.c_int32), ('skip', C.c_int32), ('reserved', C.c_int32 * 2)]
+
+
 class RenderLights(C.Structure):         # dir_render_lights
     _fields_ = [('ambient', C.c_float * 3), ('diffuse', C.c_float * 3), ('specular', C.c_float * 3), ('location', C.c_float * 3),
                 ('shininess', C.c_float)]
 
 
-ABI_VERSION = 49         # DIR_ABI_VERSION (include/dir_hip.h)
+ABI_VERSION = 50         # DIR_ABI_VERSION (include/dir_hip.h)
 DT_F32, DT_BF16, DT_F16X3, DT_F16X1, DT_F16X3P, DT_F16X1P, DT_F16 = 0, 1, 3, 4, 5, 6, 7      # DT_F16: f16 STORAGE (round 5)
 CONV_RELU, CONV_PRE_RELU = 1, 2
 
@@ -172,6 +178,10 @@ _SIGNATURES = {
     'dir_stem_prep_s2d_u8': (C.c_int, [_p, _p, C.POINTER(C.c_float), C.POINTER(C.c_float), _i, _i, _i, _i, _i, _i, _p]),
     'dir_adamw_step': (C.c_int, [_p, _p, _p, _p, C.c_longlong, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                  C.c_longlong, _p]),
+    'dir_grad_norm_workspace_bytes': (C.c_longlong, [C.c_longlong]),
+    'dir_grad_guard': (C.c_int, [_p, C.c_longlong, C.c_double, _i, C.c_double, C.c_double, _p, C.c_longlong, _p, _p]),
+    'dir_adamw_guarded_step': (C.c_int, [_p, _p, _p, _p, _p, C.c_longlong, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                         C.c_double, _p, _p]),
     'dir_stage_losses_backward': (C.c_int, [C.POINTER(LossPred), C.POINTER(LossTarget), C.c_float, _p, C.POINTER(C.c_void_p * 2),
                                             C.POINTER(C.c_void_p * 2), C.POINTER(LossPredGrad), _i, _p]),
     'dir_dense_losses_backward_workspace_bytes': (C.c_longlong, [_i, _i]),
@@ -302,7 +312,7 @@ _pending = {}
 _NO_PROFILE = ('dir_conv2d_as_supported', 'dir_conv2d_as_chain_supported', 'dir_residual_chain_supported', 'dir_abi_version', 'dir_last_error', 'dir_device_info', 'dir_launch_log_reset', 'dir_launch_log_get', 'dir_launch_log_note',
                'dir_bone_fusion_scratch_bytes', 'dir_dense_losses_workspace_bytes', 'dir_dense_losses_backward_workspace_bytes',
                'dir_gemm_f32_splitk_workspace_bytes', 'dir_bn_train_workspace_bytes', 'dir_bn_sync_workspace_bytes', 'dir_bn_frozen_workspace_bytes', 'dir_jpeg_planes_bytes', 'dir_render_workspace_bytes', 'dir_render_adjacency_bytes', 'dir_render_shaded_workspace_bytes', 'dir_colsum_workspace_bytes', 'dir_conv2d_wgrad_workspace_bytes', 'dir_conv2d_wgrad_f16x3_workspace_bytes',
-               'dir_one_euro_state_bytes')
+               'dir_one_euro_state_bytes', 'dir_grad_norm_workspace_bytes')
 
 
 def annotate(**kw):

@@ -293,6 +293,7 @@ def main(argv=None):
     from .dataset import gt_layers_from_checkpoint
     ap = argparse.ArgumentParser(description='InterHand2.6M evaluation of a DIR checkpoint on MI355X (apps/eval.py of the reference)')
     ap.add_argument('--model', type=str, default='./DIR.pth')
+    ap.add_argument('--ema', action='store_true', help="load the averaged weights (the checkpoint's 'ema' key, written by dir_amd.apps.train --ema_decay) instead of 'net'")
     ap.add_argument('--data_path', type=str, default='./data/interhand2.6m/')
     ap.add_argument('--bs', type=int, default=256)
     ap.add_argument('--root_joint', type=int, default=0)              # 0 wrist, 9 middle MCP
@@ -316,7 +317,8 @@ def main(argv=None):
                     'pa_joint_*_error.txt, pa_mesh_*_error.txt, fscore.txt and pck.txt')
     opt = ap.parse_args(argv)
     state = torch.load(opt.model, map_location='cpu', weights_only=False)
-    state = state['net'] if isinstance(state, dict) and 'net' in state else state
+    from . import checkpoint_weights
+    state = checkpoint_weights(state, opt.ema, opt.model)
     if opt.arith is not None and opt.dtype != 'f32':
         ap.error('--arith needs --dtype f32 (fp32 feature maps, f16 matrix-core arithmetic)')
     eng = DirEngine(state, dtype={'f16': torch.float16, 'bf16': torch.bfloat16, 'f32': torch.float32}[opt.dtype], root_joint=0, arith=opt.arith)     # apps/eval.py:104: DIR(21, './misc/mano')

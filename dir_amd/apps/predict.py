@@ -423,6 +423,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description='run a DIR checkpoint on full-size photos or a video: GPU hand crops by box or by tracking, '
                                              'predictions in frame pixels')
     ap.add_argument('--model', type=str, required=True)
+    ap.add_argument('--ema', action='store_true', help="load the averaged weights (the checkpoint's 'ema' key, written by dir_amd.apps.train --ema_decay) instead of 'net'")
     ap.add_argument('--input', type=str, nargs='+', required=True, help='a directory of images, or image files')
     ap.add_argument('--out', type=str, required=True)
     ap.add_argument('--boxes', type=str, default=None, help='JSON {"name": [x0, y0, x1, y1]}: the tight box around both hands')
@@ -460,7 +461,8 @@ def main(argv=None):
         with open(opt.boxes) as f:
             boxes = json.load(f)
     state = torch.load(opt.model, map_location='cpu', weights_only=False)
-    state = state['net'] if isinstance(state, dict) and 'net' in state else state
+    from . import checkpoint_weights
+    state = checkpoint_weights(state, opt.ema, opt.model)
     eng = DirEngine(state, dtype={'f16': torch.float16, 'bf16': torch.bfloat16, 'f32': torch.float32}[opt.dtype], root_joint=0)
     renderer = faces = None
     if opt.pictures or opt.obj:

@@ -14,6 +14,7 @@ The MANO buffers and faces come from the --init checkpoint, as everywhere in thi
 (train.py:207 passes cfg.root_joint), the source tree is not copied into the output folder.  Not built: more than one rank (the step
 functions average gradients when torch.distributed is initialised, but this driver shards nothing and every rank would log and save).
 """
+import contextlib
 import logging
 import math
 import os
@@ -260,12 +261,18 @@ def check_finite(total, epoch, iteration):
         raise NonFiniteLoss('the total loss is %r at epoch %d, iteration %d: stopping (see the log line above)' % (total, epoch, iteration))
 
 
-def make_optimizer(model, lr):
+def guard_fields(stats):
+    """what a printing iteration's line gains when the guarded step is on; `stats`: FlatAdamW.guard_stats()"""
+    return '[grad_norm %.4f][clip %.4f][skipped %d]' % (stats['grad_norm'], stats['clip_coef'], stats['skipped'])
+
+
+def make_optimizer(model, lr, max_grad_norm=None, skip_nonfinite=False, ema_decay=None):
     """train.py:227 on the module's own parameters (FlatAdamW moves them into one flat buffer; the module keeps seeing them)"""
     from ..optim import FlatAdamW
     from ..train.step import inactive_parameters
     named = dict(model.named_parameters())
-    opt = FlatAdamW([{'params': list(named.values()), 'initial_lr': lr}], lr)
+    opt = FlatAdamW([{'params': list(named.values()), 'initial_lr': lr}], lr, max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite,
+                    ema_decay=ema_decay)
     opt.set_inactive(inactive_parameters(named))
     return opt
 
@@ -292,12 +299,18 @@ def _count_batches(model, steps):
 
 def fit(model, batches, val_batches=None, output_root='./output', optimizer=None, schedule=None, total_epoch=50, lr=5e-4,
         lr_scheduler='cosine', step='graphed', print_iter=100, draw_iter=100, eval_interval=1, eval_dtype=None, seed=0, max_steps=None,
-        continue_train=None, name='DIR', logger=None, on_step=None, eval_penetration=False, eval_aligned=False):
+        continue_train=None, name='DIR', logger=None, on_step=None, eval_penetration=False, eval_aligned=False, max_grad_norm=None,
+        skip_nonfinite=False, ema_decay=None):
     """train() of train.py:58-91.  model: a DIR on the GPU, in training mode from here on; batches: TrainBatches of the train split (its
     `rng` is re-seeded per epoch from (seed, epoch)); val_batches: what validate() takes, or None = no validation, no best.pth.
     step: 'graphed' (GraphedTrainStep) | 'eager' (train_step) | 'module' (model(...); sum(loss).backward(); optimizer.step()).
     The driver adds no arithmetic to the step and reads a loss on printing iterations only (iteration % print_iter == 0); a NaN / inf total
     there raises NonFiniteLoss.  on_step(epoch, iteration, global_step): a hook for tests and measurements, called after every step.
+    max_grad_norm / skip_nonfinite / ema_decay (none set: nothing below happens): FlatAdamW's guarded step -- clipping by the global norm,
+    skipping a step whose gradient is not finite, an average of the weights -- decided on the device; the printing iterations' lines gain
+    '[grad_norm ..][clip ..][skipped N]' from one more read there, and NonFiniteLoss is raised when every step since the previous printing
+    iteration was skipped.  With ema_decay, validation (and so best.pth) judges the averaged weights, and both checkpoint files carry 'net'
+    (raw: what resuming needs), 'ema' and 'guard'.  No accuracy gain from either is shown anywhere in this tree.
     -> {'steps', 'epochs', 'min_error', 'last_val', 'optimizer', 'schedule', 'vis': the pictures written, 'perms': {epoch: the file indices
     in reading order}, 'lrs': {epoch: its learning rate}, 'printed': [(global step, total loss)] of the printing iterations}"""
     from ..optim import load_checkpoint, save_checkpoint
@@ -312,7 +325,13 @@ def fit(model, batches, val_batches=None, output_root='./output', optimizer=None
         os.makedirs(d, exist_ok=True)
     try:
         model.train()
-        optimizer = make_optimizer(model, lr) if optimizer is None else optimizer
+        guard_on = max_grad_norm is not None or skip_nonfinite or ema_decay is not None
+        if optimizer is None:
+            optimizer = make_optimizer(model, lr, max_grad_norm, skip_nonfinite, ema_decay)
+        elif guard_on:
+            optimizer.configure(max_grad_norm, skip_nonfinite, ema_decay)
+        guard_on = bool(getattr(optimizer, 'guarded', False))
+        since_print = 0
         schedule = make_schedule(optimizer, lr_scheduler, total_epoch) if schedule is None else schedule
         start_epoch = 0
         if continue_train:
@@ -346,12 +365,20 @@ def fit(model, batches, val_batches=None, output_root='./output', optimizer=None
                     optimizer.step()
                     outs = None
                 done += 1
+                since_print += 1
                 state['steps'] += 1
                 if print_iter and iteration % print_iter == 0:            # the loop's only host read
                     vals = torch.stack([v.detach().reshape(()).float() for v in loss.values()]).cpu().tolist()
-                    logger.info(log_line(epoch, total_epoch, iteration, n_iter, optimizer.param_groups[0]['lr'], dict(zip(loss, vals))))
+                    line = log_line(epoch, total_epoch, iteration, n_iter, optimizer.param_groups[0]['lr'], dict(zip(loss, vals)))
+                    stats = optimizer.guard_stats() if guard_on else None
+                    logger.info(line + (guard_fields(stats) if guard_on else ''))
                     state['printed'].append((state['steps'], sum(vals)))
                     check_finite(sum(vals), epoch, iteration)
+                    if guard_on and stats['skipped_in_row'] >= since_print:
+                        raise NonFiniteLoss('every one of the %d steps since the previous printing iteration was skipped for a gradient that is '
+                                            'not finite (epoch %d, iteration %d; %d skipped in a row): stopping'
+                                            % (since_print, epoch, iteration, stats['skipped_in_row']))
+                    since_print = 0
                 if draw_iter and iteration % draw_iter == 0 and outs is not None:
                     if renderer is None:
                         from ..utils import vis_utils as V
@@ -371,7 +398,9 @@ def fit(model, batches, val_batches=None, output_root='./output', optimizer=None
             logger.info('Save checkpoint to {}'.format(os.path.join(ckpt_dir, 'latest.pth')))
             state['epochs'] += 1
             if val_batches is not None and not epoch % eval_interval:
-                res = validate(model, val_batches, logger=logger, dtype=eval_dtype, penetration=eval_penetration, aligned=eval_aligned)
+                # with an average, validation and best.pth judge the averaged weights; the raw ones are back afterwards, bit for bit
+                with (optimizer.ema_weights() if getattr(optimizer, 'flat_ema', None) is not None else contextlib.nullcontext()):
+                    res = validate(model, val_batches, logger=logger, dtype=eval_dtype, penetration=eval_penetration, aligned=eval_aligned)
                 state['last_val'] = res
                 if res['error'] < state['min_error']:
                     save_checkpoint(os.path.join(ckpt_dir, 'best.pth'), model, optimizer, schedule, epoch)
@@ -433,6 +462,11 @@ def build_parser():
                     'the validation lines (best.pth is still chosen by the joint error)')
     ap.add_argument('--eval_aligned', action='store_true', help="add the last stage's PA-MPJPE and PA-MPVPE (errors after a per-hand similarity "
                     'alignment) to the validation lines (best.pth is still chosen by the unaligned joint error)')
+    ap.add_argument('--max_grad_norm', type=float, default=None, help='clip the gradient to this global L2 norm (clip_grad_norm_), on the device')
+    ap.add_argument('--skip_nonfinite', action='store_true', help='skip an optimiser step whose gradient holds a NaN or an Inf, on the device; '
+                    'the run stops when every step between two printing iterations was skipped')
+    ap.add_argument('--ema_decay', type=float, default=None, help="keep an exponential moving average of the weights (e.g. 0.9998): validation and "
+                    "best.pth judge it, checkpoints carry it as 'ema' next to 'net'")
     return ap
 
 
@@ -458,7 +492,8 @@ def main(argv=None):
                            augment=False, shuffle=False, dense_color=opt.dense_color)
     return fit(model, batches, val, output_root=opt.output_root, total_epoch=opt.total_epoch, lr=opt.lr, lr_scheduler=opt.lr_scheduler,
                step=opt.step, print_iter=opt.print_iter, draw_iter=opt.draw_iter, eval_interval=max(1, opt.eval_interval), seed=opt.seed,
-               max_steps=opt.max_steps, continue_train=opt.continue_train, name=opt.experiment_name, eval_penetration=opt.eval_penetration, eval_aligned=opt.eval_aligned)
+               max_steps=opt.max_steps, continue_train=opt.continue_train, name=opt.experiment_name, eval_penetration=opt.eval_penetration, eval_aligned=opt.eval_aligned,
+               max_grad_norm=opt.max_grad_norm, skip_nonfinite=opt.skip_nonfinite, ema_decay=opt.ema_decay)
 
 
 if __name__ == '__main__':

@@ -68,6 +68,7 @@ def main(argv=None):
     from .dataset import IMG_SIZE, gt_layers_from_checkpoint
     ap = argparse.ArgumentParser(description='draw the predicted two-hand meshes of a DIR checkpoint over the frames of a prepared split')
     ap.add_argument('--model', type=str, required=True)
+    ap.add_argument('--ema', action='store_true', help="load the averaged weights (the checkpoint's 'ema' key, written by dir_amd.apps.train --ema_decay) instead of 'net'")
     ap.add_argument('--data_path', type=str, required=True)
     ap.add_argument('--split', type=str, default='test', choices=['train', 'val', 'test'])
     ap.add_argument('--out', type=str, required=True)
@@ -79,7 +80,8 @@ def main(argv=None):
     ap.add_argument('--joints', action='store_true', help='draw the predicted 2-D joints on the overlay')
     opt = ap.parse_args(argv)
     state = torch.load(opt.model, map_location='cpu', weights_only=False)
-    state = state['net'] if isinstance(state, dict) and 'net' in state else state
+    from . import checkpoint_weights
+    state = checkpoint_weights(state, opt.ema, opt.model)
     eng = DirEngine(state, dtype={'f16': torch.float16, 'bf16': torch.bfloat16, 'f32': torch.float32}[opt.dtype], root_joint=0)
     mano = gt_layers_from_checkpoint(state)
     # the dense table only feeds render_densepose, which is not used here

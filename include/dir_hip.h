@@ -29,7 +29,7 @@ extern "C" {
 #define DIR_E_LAUNCH (-2)   /* hipLaunchKernel / HIP runtime error          */
 #define DIR_E_NODEVICE (-3) /* no gfx950 device visible                     */
 
-#define DIR_ABI_VERSION 49
+#define DIR_ABI_VERSION 50
 
 int dir_abi_version(void);
 const char* dir_last_error(void);
@@ -956,6 +956,53 @@ int dir_dense_losses_forward(const float* seg_logits, const float* dense_pred, c
  * operation order.  step = 1-based update count (the value torch keeps in state['step'] AFTER this update). */
 int dir_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long long n, double lr, double beta1,
                    double beta2, double eps, double weight_decay, long long step, void* stream);
+
+/* Guarded AdamW step (ABI 50): gradient clipping by the global norm, skipping of a step whose gradient is not finite, and an exponential
+ * moving average of the parameters, decided on the device -- the host reads nothing in order to go on.  The reference has none of the
+ * three: the rule below is this project's own (clip_grad_norm_'s coefficient, GradScaler's way of skipping, timm ModelEmaV2's average),
+ * restated in numpy by tests/helpers/guarded_step_ref.py.  Per step: ONE dir_grad_guard over the whole gradient (two small launches), then
+ * one dir_adamw_guarded_step per parameter range (one streaming launch each), all on the same stream.
+ *
+ * dir_grad_guard(grad[n], ...):
+ *   sumsq     = sum_i (double)g_i * (double)g_i.  Stage one: a fixed grid (a function of n only) of 256-thread workgroups, each thread
+ *               accumulating its grid-stride share in double, each workgroup summing its 256 values in a fixed tree and writing ONE
+ *               double to workspace[workgroup index]; stage two: one workgroup sums those in index order and the same tree.  No
+ *               floating-point atomics, no completion counters: the same n and bytes give the same bits on every run.  A gradient of
+ *               1e30 squares to 1e60 in double (finite).  workspace: dir_grad_norm_workspace_bytes(n) bytes (device, 8-byte aligned;
+ *               a pure host function, -1 for n <= 0).
+ *   norm      = sqrt(sumsq);  nonfinite = !isfinite(sumsq)  (one NaN or Inf anywhere in grad[0..n) sets it)
+ *   coef      = (float)min(1.0, max_norm / (norm + 1e-6))   (max_norm = +inf: 1.0f; min(1.0, NaN) = 1.0)
+ *   skip      = skip_nonfinite && nonfinite
+ *   skip:       skipped += 1, skipped_in_row += 1; bc1, bc2_sqrt keep their values
+ *   otherwise:  applied += 1, skipped_in_row = 0, clipped += (coef < 1);
+ *               bc1 = 1 - beta1^applied (double), bc2_sqrt = (float)sqrt(1 - beta2^applied): dir_adamw_step's prefactors for
+ *               step = applied.  A skipped step does not advance AdamW's step count.
+ *   The counters are read-modify-written: the caller zeroes the state once (or writes the counts to continue from) and never again.
+ *
+ * dir_adamw_guarded_step(...): dir_adamw_step's arithmetic, operation for operation, with
+ *   g'        = g * coef                       (one float multiply, not contracted: the bits g.mul_(coef) leaves)
+ *   step_size = (float)(lr / state->bc1), bc2_sqrt = state->bc2_sqrt;  lr, betas, eps, weight_decay are host arguments as before
+ *   ema       (may be NULL) after the parameter update, with w = (float)(1 - ema_decay), not contracted, torch's lerp_(p, w):
+ *               e = e + w * (p_new - e)            for w <  0.5  (every decay in use)
+ *               e = p_new - (p_new - e) * (1 - w)  for w >= 0.5  (decay = 0 returns p_new itself)
+ *   state->skip set: the kernel returns before any load or store: param, exp_avg, exp_avg_sq and ema keep their bits.
+ * Both check their arguments (null pointers, alignment, n <= 0, max_norm <= 0 or NaN, ema_decay outside [0, 1], workspace too small)
+ * before anything is launched. */
+typedef struct dir_guard_state {
+    double sumsq, norm;                 /* of the last dir_grad_guard */
+    double bc1;                         /* 1 - beta1^applied */
+    long long applied, skipped, skipped_in_row, clipped;
+    float coef;                         /* of the last dir_grad_guard */
+    float bc2_sqrt;                     /* sqrt(1 - beta2^applied) */
+    int32_t nonfinite, skip;            /* of the last dir_grad_guard */
+    int32_t reserved[2];
+} dir_guard_state;     /* 80 bytes */
+long long dir_grad_norm_workspace_bytes(long long n);
+int dir_grad_guard(const float* grad, long long n, double max_norm, int skip_nonfinite, double beta1, double beta2, void* workspace,
+                   long long workspace_bytes, dir_guard_state* state, void* stream);
+int dir_adamw_guarded_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, long long n, double lr,
+                           double beta1, double beta2, double eps, double weight_decay, double ema_decay, const dir_guard_state* state,
+                           void* stream);
 
 /* a13 backward, first step of the training backward pass (8f rank 2): gradients of (sum_k grad_out[k] * term_k) w.r.t. the predictions
  * the terms read -- what autograd gives through models/loss.py / models/lovasz_loss.py / nn.CrossEntropyLoss as models/dir.py:562-592
