@@ -147,7 +147,7 @@ class RenderLights(C.Structure):         # dir_render_lights
                 ('shininess', C.c_float)]
 
 
-ABI_VERSION = 50         # DIR_ABI_VERSION (include/dir_hip.h)
+ABI_VERSION = 51         # DIR_ABI_VERSION (include/dir_hip.h)
 DT_F32, DT_BF16, DT_F16X3, DT_F16X1, DT_F16X3P, DT_F16X1P, DT_F16 = 0, 1, 3, 4, 5, 6, 7      # DT_F16: f16 STORAGE (round 5)
 CONV_RELU, CONV_PRE_RELU = 1, 2
 
@@ -277,6 +277,7 @@ _SIGNATURES = {
     'dir_mano_forward': (C.c_int, [C.POINTER(ManoTables), _p, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _i, _p]),
     'dir_jpeg_planes_bytes': (C.c_longlong, [C.c_longlong]),
     'dir_jpeg_decode_records': (C.c_int, [_p, C.c_longlong, _i, _i, _i, _p, C.c_longlong, _p, _p, _p]),
+    'dir_jpeg_encode_records': (C.c_int, [_p, _i, _i, _i, _i, _p, _p, _p, C.c_longlong, _p]),
     'dir_train_noise_field': (C.c_int, [C.c_ulonglong, _p, _i, _p]),
     'dir_train_augment_images': (C.c_int, [_p, _p, _p, _p, _p, C.c_ulonglong, C.POINTER(C.c_float), C.POINTER(C.c_float), _p, _p, _p, _p, _p,
                                            _p, _i, _p]),

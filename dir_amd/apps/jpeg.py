@@ -11,6 +11,15 @@ the decoded frame, so the host -> device traffic is unchanged while the host's w
 what saturated the 16-CPU quota at 22 k images/s, profiles/r04_fromdisk_sweep_flag_ring.txt).  Files the entropy decoder refuses (progressive,
 arithmetic, CMYK) or that are not 256x256 are decoded the ordinary way on the host (dataset.decode_bgr) and travel as PIXEL records.
 
+The ENCODE path is the mirror image (cv.imwrite of dataset/prepare_data.py:174-214, the mask/ and dense/ frames):
+
+    GPU    (dir_jpeg_encode_records, csrc/jpeg_enc.hip)                        uint8 frames [B,H,W,3] -> colour conversion, 4:2:0 downsampling, integer
+                                                                               forward DCT, quantisation -> one record per frame (RecordEncoder)
+    host   (dir_jpeg_encode_record, include/dir_jpeg_enc.h)                    record -> Huffman coding + file syntax (record_to_bytes, write_record)
+
+and the file equals the one libjpeg(-turbo) writes for the frame at the same quality, byte for byte (tests/test_jpeg_enc_ref.py,
+tests/test_gpu_jpeg_enc.py).  jpeg_round_trip: encode then decode on the device = the pixels cv.imread gives back from such a file.
+
 Plumbing only: pointers, sizes, error codes.  No GPU call happens in a worker process (libdir_jpeg.so has no GPU runtime in it)."""
 import ctypes as C
 import os
@@ -41,6 +50,15 @@ def host_lib():
         lib.dir_jpeg_abi_version.restype = C.c_int
         if lib.dir_jpeg_abi_version() != 1:
             raise _capi.DirHipError('libdir_jpeg.so ABI version %d != 1' % lib.dir_jpeg_abi_version())
+        lib.dir_jpeg_encode_record.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        lib.dir_jpeg_encode_record.restype = C.c_int
+        lib.dir_jpeg_encode_bound.argtypes = [C.c_void_p, C.c_size_t]
+        lib.dir_jpeg_encode_bound.restype = C.c_size_t
+        lib.dir_jpeg_quality_tables.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+        lib.dir_jpeg_quality_tables.restype = C.c_int
+        lib.dir_jpeg_enc_abi_version.restype = C.c_int
+        if lib.dir_jpeg_enc_abi_version() != 1:
+            raise _capi.DirHipError('libdir_jpeg.so encoder ABI version %d != 1' % lib.dir_jpeg_enc_abi_version())
         _host = lib
     return _host
 
@@ -105,3 +123,94 @@ class RecordDecoder(object):
         e = int(self.err.item())
         if e:
             raise _capi.DirHipError('dir_jpeg_decode_records: record %d of a batch did not describe a %dx%d image' % (e - 1, self.H, self.W))
+
+
+def quality_tables(quality):
+    """libjpeg's jpeg_set_quality(quality, force_baseline) -> (luma, chroma) uint16 [64] in natural order (dir_jpeg_quality_tables)"""
+    luma, chroma = np.zeros(64, np.uint16), np.zeros(64, np.uint16)
+    if host_lib().dir_jpeg_quality_tables(int(quality), luma.ctypes.data, chroma.ctypes.data) != 0:
+        raise ValueError('JPEG quality %r is not in 1..100' % (quality,))
+    return luma, chroma
+
+
+def record_to_bytes(row):
+    """one coefficient record (a contiguous uint8 numpy array, at least the record's size) -> the bytes of its baseline JFIF file
+    (dir_jpeg_encode_record: Huffman coding + file syntax on the host)"""
+    lib = host_lib()
+    row = np.ascontiguousarray(row, np.uint8)
+    cap = int(lib.dir_jpeg_encode_bound(row.ctypes.data, row.size))
+    out = np.empty(max(cap, 1), np.uint8)
+    n = C.c_size_t(0)
+    rc = lib.dir_jpeg_encode_record(row.ctypes.data, row.size, out.ctypes.data, cap, C.byref(n)) if cap else -2
+    if rc != 0:
+        raise ValueError('not an encodable coefficient record (dir_jpeg_encode_record returned %d)' % rc)
+    return out[:n.value].tobytes()
+
+
+def write_record(path, row):
+    """one coefficient record -> a .jpg file"""
+    data = record_to_bytes(row)
+    with open(path, 'wb') as f:
+        f.write(data)
+    return len(data)
+
+
+class RecordEncoder(object):
+    """uint8 frames [B,H,W,3] on the GPU -> coefficient records on the GPU (dir_jpeg_encode_records), written into a caller's buffer
+    [B, stride] uint8.  4:2:0, H and W multiples of 16 and at most 4096; the quantisation tables of `quality` are made once, on the host.
+    A record becomes the file libjpeg writes for the frame at that quality through record_to_bytes / write_record."""
+
+    def __init__(self, batch, size, quality=95, channel_order='bgr'):
+        """size: the frames' edge, or (height, width); channel_order: 'bgr' (what cv.imwrite receives, the project's frames) or 'rgb'"""
+        self.batch = batch
+        self.H, self.W = (size, size) if isinstance(size, int) else size
+        if channel_order not in ('bgr', 'rgb'):
+            raise ValueError("channel_order must be 'bgr' or 'rgb'")
+        self.order = 1 if channel_order == 'rgb' else 0
+        self.quality = quality
+        self.luma, self.chroma = quality_tables(quality)
+        n = int(host_lib().dir_jpeg_record_bytes(self.W, self.H, 2, 2, 3))
+        self.record_bytes = (n + 15) // 16 * 16
+
+    def __call__(self, frames, records, n=None):
+        """frames: uint8 cuda [B,H,W,3]; records: uint8 cuda [B, stride >= record_bytes]; encodes the first n (default all) on the current stream"""
+        _capi.require_cuda(frames, records)
+        assert frames.dtype == torch.uint8 and frames.is_contiguous() and tuple(frames.shape[1:]) == (self.H, self.W, 3)
+        assert records.dtype == torch.uint8 and records.is_contiguous() and records.dim() == 2
+        n = frames.shape[0] if n is None else n
+        assert n <= self.batch and frames.shape[0] >= n and records.shape[0] >= n
+        with torch.cuda.device(frames.device):
+            _capi.check(_capi.lib().dir_jpeg_encode_records(_capi.ptr(frames), n, self.H, self.W, self.order, self.luma.ctypes.data, self.chroma.ctypes.data,
+                                                            _capi.ptr(records), records.shape[1], _capi.stream_ptr()), 'dir_jpeg_encode_records')
+        return records
+
+
+class RoundTrip(object):
+    """frames -> records -> frames on the device (RecordEncoder + RecordDecoder, two entry points, buffers kept per instance): the pixels
+    cv.imread / decode_bgr return from the file cv.imwrite writes for each frame at `quality`"""
+
+    def __init__(self, batch, size=256, quality=95, channel_order='bgr', device='cuda'):
+        self.enc = RecordEncoder(batch, size, quality, channel_order)
+        self.dec = RecordDecoder(batch, self.enc.record_bytes, size, device)
+        self.records = torch.empty(batch, self.enc.record_bytes, dtype=torch.uint8, device=device)
+
+    def __call__(self, frames, out=None):
+        """frames: uint8 cuda [B,H,W,3] in the encoder's channel order -> uint8 [B,H,W,3] in the same order (a new tensor unless `out` is given)"""
+        n = frames.shape[0]
+        out = torch.empty_like(frames) if out is None else out
+        self.enc(frames, self.records, n)
+        self.dec(self.records, out, n)                                   # (the decoder writes B, G, R)
+        return out if self.enc.order == 0 else out.flip(-1)
+
+
+_round_trips = {}
+
+
+def jpeg_round_trip(frames, quality=95):
+    """uint8 cuda BGR frames [B,H,W,3] -> the frames after cv.imwrite(quality) + cv.imread, computed on the device.  The RoundTrip instances
+    (tables, record buffer, decoder scratch) are kept per (device, batch, size, quality)."""
+    key = (frames.device, frames.shape[0], tuple(frames.shape[1:3]), int(quality))
+    rt = _round_trips.get(key)
+    if rt is None:
+        rt = _round_trips[key] = RoundTrip(frames.shape[0], key[2], quality, 'bgr', frames.device)
+    return rt(frames)

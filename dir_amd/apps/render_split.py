@@ -1,7 +1,7 @@
 """dataset/prepare_data.py:174-214 (render_data) for the prepared split: <split>/mask/<idx>.jpg and <split>/dense/<idx>.jpg from the
 ground-truth MANO meshes of <split>/anno/<idx>.pkl, on the GPU.
 
-    python -m dir_amd.apps.render_split --save_path ROOT --model CKPT --dense_color PKL [--split train] [--bs 256] [--workers N]
+    python -m dir_amd.apps.render_split --save_path ROOT --model CKPT --dense_color PKL [--split train] [--bs 256] [--workers N] [--gpu_encode]
 
 Batches of annotations (InterHandSplit.anno) go through gt_batch with the GT layers of the checkpoint (gt_layers_from_checkpoint, which
 already carries the fix_shape correction), then the two-hand rasteriser (dir_amd.utils.vis_utils.render_frames, 256 x 256 as IMG_SIZE).
@@ -9,6 +9,10 @@ The frames are written as cv.imwrite writes them by default: JPEG quality 95, 4:
 same libjpeg), the channels reversed first so that cv.imread / decode_bgr gives back the renderer's array channel order.  Annotation
 reads and JPEG encodes run in worker processes, at most 16 of them.  The reference's render_data also makes an empty hms/ folder; it
 is made here as well.
+
+--gpu_encode: the JPEG encode is split as the decode of the from-files path is.  The GPU does everything before the Huffman coder
+(dir_amd.apps.jpeg.RecordEncoder: colour conversion, 4:2:0 downsampling, forward DCT, quantisation -> one coefficient record per frame);
+the worker processes Huffman-code the records and write the files (write_record).  The files are byte-identical to the default path's.
 """
 import os
 import time
@@ -37,14 +41,23 @@ def _write(data_path, split, idx, masks, dense):
     return len(idx)
 
 
+def _write_records(data_path, split, idx, masks, dense):
+    """--gpu_encode: the workers' half -- coefficient records [n, stride] uint8 -> files"""
+    from .jpeg import write_record
+    for j, i in enumerate(idx):
+        write_record(os.path.join(data_path, split, 'mask', '%d.jpg' % i), masks[j])
+        write_record(os.path.join(data_path, split, 'dense', '%d.jpg' % i), dense[j])
+    return len(idx)
+
+
 def default_workers():
     n = len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else (os.cpu_count() or 1)
     return max(1, min(MAX_WORKERS, n))
 
 
-def render_split(data_path, state, dense_color, split='train', bs=256, workers=None, device='cuda', progress=None):
+def render_split(data_path, state, dense_color, split='train', bs=256, workers=None, device='cuda', progress=None, gpu_encode=False):
     """render_data(data_path, split) with the GT layers of checkpoint `state` and the dense table `dense_color` (path or [778,3] array)
-    -> (images written, seconds)"""
+    -> (images written, seconds).  gpu_encode: everything of the JPEG encode before the Huffman coder runs on the GPU (same files)."""
     import multiprocessing as mp
     import torch
     from .dataset import IMG_SIZE, InterHandSplit, gt_batch, gt_layers_from_checkpoint
@@ -60,6 +73,12 @@ def render_split(data_path, state, dense_color, split='train', bs=256, workers=N
     ws = torch.empty(int(_capi.lib().dir_render_workspace_bytes(bs)), dtype=torch.uint8, device=device)
     batches = [list(range(s, min(n, s + bs))) for s in range(0, n, bs)]
     chunk = max(1, -(-bs // workers))
+    enc = recs = None
+    if gpu_encode:
+        from .jpeg import RecordEncoder
+        enc = RecordEncoder(2 * bs, IMG_SIZE, quality=95, channel_order='bgr')       # the renderer's arrays are what cv.imwrite receives
+        recs = torch.empty(2 * bs, enc.record_bytes, dtype=torch.uint8, device=device)
+    write = _write_records if gpu_encode else _write
     t0 = time.time()
     done = 0
     with mp.get_context('spawn').Pool(workers) as pool:
@@ -72,11 +91,18 @@ def render_split(data_path, state, dense_color, split='train', bs=256, workers=N
             gt = gt_batch(mano, an)
             verts = torch.cat((gt[1], gt[3]), dim=1).contiguous()
             m, d = V.render_frames(verts, faces, gt[8], colors, IMG_SIZE, workspace=ws)
-            m, d = m.cpu().numpy(), d.cpu().numpy()
+            if gpu_encode:
+                nb = len(idx)
+                enc(m, recs[:nb], nb)
+                enc(d, recs[bs:bs + nb], nb)
+                host = recs.cpu().numpy()
+                m, d = host[:nb], host[bs:bs + nb]
+            else:
+                m, d = m.cpu().numpy(), d.cpu().numpy()
             while len(pending) > 2 * workers:                              # bounded: at most ~2 batches of frames in flight
                 done += pending.pop(0).get()
             for j in range(0, len(idx), chunk):
-                pending.append(pool.apply_async(_write, (data_path, split, idx[j:j + chunk], m[j:j + chunk], d[j:j + chunk])))
+                pending.append(pool.apply_async(write, (data_path, split, idx[j:j + chunk], m[j:j + chunk], d[j:j + chunk])))
             if progress:
                 progress(done, n)
         for p in pending:
@@ -94,11 +120,12 @@ def main(argv=None):
     ap.add_argument('--split', type=str, default='train', choices=['train', 'val', 'test'])
     ap.add_argument('--bs', type=int, default=256)
     ap.add_argument('--workers', type=int, default=None, help='encode processes (default: the CPUs this process may use, at most 16)')
+    ap.add_argument('--gpu_encode', action='store_true', help='JPEG encode split like the decode: DCT + quantisation on the GPU, Huffman coding in the workers (same files)')
     opt = ap.parse_args(argv)
     state = torch.load(opt.model, map_location='cpu', weights_only=False)
     state = state['net'] if isinstance(state, dict) and 'net' in state else state
     from dir_amd.apps import render_split as mod                          # workers pickle the module's functions by this name, not __main__
-    n, sec = mod.render_split(opt.save_path, state, opt.dense_color, opt.split, opt.bs, opt.workers,
+    n, sec = mod.render_split(opt.save_path, state, opt.dense_color, opt.split, opt.bs, opt.workers, gpu_encode=opt.gpu_encode,
                               progress=lambda k, total: print('\r%d / %d' % (k, total), end='', flush=True))
     print('\n%d images (mask + dense) in %.1f s: %.0f images/s' % (n, sec, n / max(sec, 1e-9)))
     return n

@@ -204,14 +204,17 @@ class TrainBatches(object):
     dense_color: the dense colour table (the [778,3] array in 0..1 of get_dense_color_path(), or the pickle's path).  Given, mask and
     dense are not read from files: they are rendered per batch (csrc/render.hip, render_data's rules) from the camera-frame vertices of
     gt_batch, whose tuple augment_batch then reuses, so the ground-truth MANO runs once; only img/ is decoded.  These frames are the
-    arrays cv.imwrite would receive, without the JPEG round trip the files have been through, so they are not the file path's bytes.
+    arrays cv.imwrite would receive.  With jpeg_round_trip=False (the default) they go to augment_batch as they are, without the JPEG
+    round trip the files have been through, so they are not the file path's bytes.  With jpeg_round_trip=True they pass through the JPEG
+    encode and decode at quality 95 on the device first (dir_amd.apps.jpeg.RoundTrip: dir_jpeg_encode_records, then
+    dir_jpeg_decode_records), and are then exactly what the file path decodes from the mask/ and dense/ files render_split writes.
     The faces are the right GT layer's (ManoLayer.get_faces()); a layer without faces (a checkpoint without th_faces) is an error.
 
     shuffle=False: every pass reads the split in file order (the reference's test loader, train.py:215-220; drop_last as well) and draws
     no permutation.  `self.last_perm` holds the file indices of the pass that was started last, in the order they are read."""
 
     def __init__(self, data_path, mano_layer, split='train', batch_size=32, workers=8, seed=0, augment=True, records=True, device='cuda',
-                 dense_color=None, shuffle=True):
+                 dense_color=None, shuffle=True, jpeg_round_trip=False):
         from .dataset import InterHandSplit
         self.data_path, self.split, self.mano_layer = data_path, split, mano_layer
         self.bs, self.workers, self.augment, self.records = batch_size, workers, augment, records
@@ -221,12 +224,17 @@ class TrainBatches(object):
         self.n = len(InterHandSplit(data_path, split))
         self.epoch = 0
         self.last_params, self.last_seed = None, None
-        self.render = None
+        self.render = self.round_trip = None
+        if jpeg_round_trip and dense_color is None:
+            raise ValueError('TrainBatches: jpeg_round_trip applies to rendered targets (dense_color=...)')
         if dense_color is not None:
             from ..utils import vis_utils as V
             self.render = (torch.from_numpy(V.faces_from_layers(mano_layer)).to(self.device),
                            torch.from_numpy(V.load_dense_colors(dense_color)).to(self.device),
                            torch.empty(int(_capi.lib().dir_render_workspace_bytes(batch_size)), dtype=torch.uint8, device=self.device))
+            if jpeg_round_trip:
+                from .jpeg import RoundTrip
+                self.round_trip = RoundTrip(batch_size, IMG_SIZE, quality=95, channel_order='bgr', device=self.device)
 
     def __len__(self):
         return self.n // self.bs
@@ -281,6 +289,8 @@ class TrainBatches(object):
                 faces, colors, ws = self.render
                 verts = torch.cat((gt[1], gt[3]), dim=1).contiguous()
                 masks, dense = render_frames(verts, faces, gt[8], colors, S, workspace=ws)
+                if self.round_trip is not None:
+                    masks, dense = self.round_trip(masks), self.round_trip(dense)
                 yield augment_batch(fr, masks, dense, gt, pr, seed=seed, augment=self.augment)
             if dec is not None:
                 dec.check()                                                # a record that was not a 256x256 image would have left its frame stale

@@ -88,18 +88,20 @@ def build(force=False, verbose=True):
 
 
 JPEG_SRC = os.path.join(CSRC, 'jpeg_huff.c')
+JPEG_ENC_SRC = os.path.join(CSRC, 'jpeg_enc_huff.c')
 JPEG_LIB = os.path.join(LIBDIR, 'libdir_jpeg.so')
 
 
 def build_jpeg_host(force=False, verbose=True):
-    """lib/libdir_jpeg.so: the HOST half of the from-files path (csrc/jpeg_huff.c: baseline-JPEG entropy decode, plain C, no GPU runtime -- the
-    decode worker processes load it), compiled with gcc"""
+    """lib/libdir_jpeg.so: the HOST halves of the JPEG paths (csrc/jpeg_huff.c: baseline-JPEG entropy decode, include/dir_jpeg.h;
+    csrc/jpeg_enc_huff.c: Huffman coding + file syntax, include/dir_jpeg_enc.h; plain C, no GPU runtime -- the decode and encode worker
+    processes load it), compiled with gcc"""
     os.makedirs(LIBDIR, exist_ok=True)
-    hdr = os.path.join(HERE, '..', 'include', 'dir_jpeg.h')
-    if not force and os.path.exists(JPEG_LIB) and os.path.getmtime(JPEG_LIB) > max(os.path.getmtime(JPEG_SRC), os.path.getmtime(hdr)):
+    deps = [JPEG_SRC, JPEG_ENC_SRC] + [os.path.join(HERE, '..', 'include', h) for h in ('dir_jpeg.h', 'dir_jpeg_enc.h')]
+    if not force and os.path.exists(JPEG_LIB) and os.path.getmtime(JPEG_LIB) > max(os.path.getmtime(d) for d in deps):
         return JPEG_LIB
     cc = shutil.which('gcc') or shutil.which('cc') or hipcc()
-    r = subprocess.run([cc, '-O3', '-std=c11', '-Wall', '-Wextra', '-fPIC', '-shared', JPEG_SRC, '-o', JPEG_LIB], capture_output=True, text=True)
+    r = subprocess.run([cc, '-O3', '-std=c11', '-Wall', '-Wextra', '-fPIC', '-shared', JPEG_SRC, JPEG_ENC_SRC, '-o', JPEG_LIB], capture_output=True, text=True)
     if r.returncode != 0:
         raise RuntimeError('building libdir_jpeg.so failed:\n%s\n%s' % (r.stdout, r.stderr))
     if verbose:

@@ -29,7 +29,7 @@ extern "C" {
 #define DIR_E_LAUNCH (-2)   /* hipLaunchKernel / HIP runtime error          */
 #define DIR_E_NODEVICE (-3) /* no gfx950 device visible                     */
 
-#define DIR_ABI_VERSION 50
+#define DIR_ABI_VERSION 51
 
 int dir_abi_version(void);
 const char* dir_last_error(void);
@@ -1035,6 +1035,40 @@ int dir_dense_losses_backward(const float* seg_logits, const float* dense_pred, 
 long long dir_jpeg_planes_bytes(long long record_bytes);
 int dir_jpeg_decode_records(const void* records, long long record_stride, int B, int H, int W, void* planes_scratch, long long scratch_bytes, void* out_bgr,
                             int32_t* err_flag, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------------------------
+ * To files: the GPU half of the JPEG ENCODE (ABI 51), the mirror image of dir_jpeg_decode_records.  cv.imwrite of the reference's
+ * dataset/prepare_data.py:174-214 (mask/ and dense/ frames) = libjpeg's default compression.  This entry point does everything before the
+ * Huffman coder, in one launch: uint8 frames [B,H,W,3] (HWC; channel_order 0 = B,G,R -- what cv.imwrite receives, the project's frame
+ * convention -- or 1 = R,G,B) -> B coefficient records `record_stride` bytes apart, each a dir_jpeg_header + int16 coefficients
+ * [component][block row][block column][64] in natural order: byte for byte what dir_jpeg_decode_coefficients (include/dir_jpeg.h) writes
+ * when it reads the file libjpeg(-turbo) writes for the frame.  The host turns a record into that file (include/dir_jpeg_enc.h:
+ * dir_jpeg_encode_record).  Bytes of a slot beyond the record (dir_jpeg_record_bytes(W, H, 2, 2, 3)) are not touched.
+ *
+ * Scope: three components, 4:2:0, 8-bit samples, H and W multiples of 16 (whole MCUs: no edge replication, no dummy blocks), each at most
+ * 4096, table entries 1..255.  Anything else returns DIR_E_INVALID before any launch (callers keep their host encoder for such frames).
+ *
+ * The rule (libjpeg's, integer and exact; int32 suffices for 8-bit samples):
+ *   tables     luma_q / chroma_q: HOST pointers to uint16[64] in natural order, e.g. dir_jpeg_quality_tables (jpeg_set_quality(q, TRUE):
+ *              s = 5000 / q for q < 50, else 200 - 2 q; entry = clamp((base * s + 50) / 100, 1, 255) over the Annex K tables); passed to
+ *              the kernel by value and copied into every header (quant[0] = luma, quant[1] = quant[2] = chroma)
+ *   colour     jccolor.c, FIX(x) = int(x * 65536 + 0.5):
+ *                Y  = ( FIX(.299) R + FIX(.587) G + FIX(.114) B + 32768) >> 16
+ *                Cb = (-FIX(.16874) R - FIX(.33126) G + FIX(.5) B + (128 << 16) + 32767) >> 16
+ *                Cr = ( FIX(.5) R - FIX(.41869) G - FIX(.08131) B + (128 << 16) + 32767) >> 16
+ *   chroma     jcsample.c h2v2_downsample without smoothing: (a + b + c + d + bias) >> 2 over each 2 x 2 group, bias 1 for even output
+ *              columns and 2 for odd ones
+ *   DCT        jfdctint.c ("islow") on sample - 128, CONST_BITS 13, PASS1_BITS 2: rows first (results scaled up by 4), then columns
+ *              (DESCALE by PASS1_BITS for outputs 0 and 4, by CONST_BITS + PASS1_BITS for the others), its twelve constants,
+ *              DESCALE(x, n) = (x + (1 << (n - 1))) >> n; the results carry libjpeg's factor 8
+ *   quantise   sign(c) * ((|c| + (8 q >> 1)) / (8 q))   (jcdctmgr.c; computed with an exact reciprocal: the same integers)
+ *   header     magic DIR_JPEG_MAGIC, width, height, ncomp 3, hmax = vmax = 2, mcux = W / 16, mcuy = H / 16, h = v = {2, 1, 1},
+ *              blocks_x = {2 mcux, mcux, mcux}, blocks_y likewise, coef_offset = {0, 256 n, 320 n} and total_coef = 384 n for n = mcux mcuy,
+ *              the tables, reserved words zero
+ * An MCU depends on nothing but its own 16 x 16 pixels: no atomics, no scratch, no workspace, no host read; capturable in a graph; an
+ * image gives the same bytes in any slot of any batch.  frames: 4-byte aligned; records: 16-byte aligned, record_stride a multiple of 16. */
+int dir_jpeg_encode_records(const void* frames, int B, int H, int W, int channel_order, const uint16_t* luma_q, const uint16_t* chroma_q,
+                            void* records, long long record_stride, void* stream);
 
 
 /* ---- training input: dataset/interhand.py:__getitem__ of split 'train' (utils/utils.py:202-207, 406-533) for a batch (csrc/augment.hip) ----
