@@ -1,0 +1,139 @@
+"""MANO parameters for hands that come without them: 3-D joints, meshes (a dataset's, or another model's output) or 2-D keypoints -> the
+64-vector of this tree (6D root, 45 PCA coefficients, 10 betas, 3 camera scalars), fitted on the GPU by dir_mano_fit (utils/mano_fit.py).
+
+    python -m dir_amd.apps.fit_mano --model CKPT --targets T.npz --out O.npz [--iters 200] [--lr 0.1] [--lr_root --lr_pca --lr_betas --lr_cam]
+                                    [--bs 256] [--center 0] [--cam_scale 1.0] [--w_verts 1e4 --w_joints 1e4 --w_uv 1 --w_pca 0 --w_beta 0
+                                    --w_init 0] [--ema]
+
+The MANO tables come from the checkpoint (init_regressor.mano_layer_{left,right}.th_*), as in apps.predict.  T.npz holds, per side in
+(left, right), any of  verts_<side> [N,778,3],  joints_<side> [N,21,3] with joints_conf_<side> [N,21],  joint_uv_<side> [N,21,2] (the crop's
+-1..1 coordinates, as pd_joint_uv_*) with uv_conf_<side> [N,21],  and optionally init_<side> [N,64] (default: neutral_para(N, --cam_scale)).
+3-D targets are relative to joint --center of the same hand (joint order of pd_joint_xyz_*; -1: not centred); a confidence of 0 drops an
+entry, which may then hold NaN.  A side with no target is left out.  O.npz holds para_<side> [N,64], the fitted verts_ / joints_ / joint_uv_<side>,
+mse_before_<side> and mse_after_<side> [N,3] (mean squared residual of the vertices, 3-D joints and 2-D joints, unweighted) and status_<side>
+[N] (bit 0 reflection, bit 1 non-finite input: passed through, bit 2 a step went non-finite: stopped there).  The last line printed is
+"N hands in T s".  The defaults are NOT tuned on real MANO tables or real keypoints.
+"""
+import time
+
+import numpy as np
+
+SIDES = ('left', 'right')
+TARGETS = (('verts', (778, 3)), ('joints', (21, 3)), ('joints_conf', (21,)), ('joint_uv', (21, 2)), ('uv_conf', (21,)))
+
+
+def read_targets(npz):
+    """-> {side: {name: float32 array}} for the sides that have a target; ValueError on a wrong shape or a confidence without its target"""
+    out = {}
+    for side in SIDES:
+        d = {}
+        for name, shape in TARGETS + (('init', (64,)),):
+            k = '%s_%s' % (name, side)
+            if k in npz:
+                a = np.asarray(npz[k], np.float32)
+                if a.ndim != len(shape) + 1 or tuple(a.shape[1:]) != shape:
+                    raise ValueError('fit_mano: %s must be [N%s], got %s' % (k, ''.join(',%d' % s for s in shape), list(a.shape)))
+                d[name] = a
+        if not any(k in d for k in ('verts', 'joints', 'joint_uv')):
+            if d:
+                raise ValueError('fit_mano: %s has %s but no target (verts, joints or joint_uv)' % (side, sorted(d)))
+            continue
+        if ('joints_conf' in d and 'joints' not in d) or ('uv_conf' in d and 'joint_uv' not in d):
+            raise ValueError('fit_mano: %s has confidences without their target' % side)
+        if len({a.shape[0] for a in d.values()}) != 1:
+            raise ValueError('fit_mano: the arrays of %s differ in their first dimension' % side)
+        out[side] = d
+    if not out:
+        raise ValueError('fit_mano: the targets hold none of ' + ', '.join('%s_<side>' % n for n in ('verts', 'joints', 'joint_uv')))
+    return out
+
+
+def tables_from_checkpoint(state, center=0, device='cuda'):
+    """{side: _capi.ManoTables} from the checkpoint's th_* buffers, and the list that keeps their device tensors alive"""
+    import torch  # noqa: F401
+
+    from ..engine import pack_mano
+    keep = []
+    sd = {k: v.detach().to(device) for k, v in state.items() if k.startswith('init_regressor.mano_layer_')}
+    return {s: pack_mano(sd, 'init_regressor.mano_layer_' + s, s, None if center < 0 else center, keep) for s in SIDES}, keep
+
+
+def fit_targets(tables, targets, iters=200, lr=0.1, weights=None, bs=256, cam_scale=1.0, device='cuda'):
+    """targets: read_targets' dict -> {side: {para, verts, joints, joint_uv, mse_before, mse_after, status}} (numpy).  Both sides with the same N go
+    through one launch per batch as a pair, otherwise one side at a time."""
+    import torch
+
+    from ..utils import mano_fit as MF
+    sides = [s for s in SIDES if s in targets]
+    n_of = lambda s: next(iter(targets[s].values())).shape[0]  # noqa: E731
+    groups = [sides] if len(sides) == 2 and n_of(sides[0]) == n_of(sides[1]) else [[s] for s in sides]
+    out = {s: {} for s in sides}
+    for grp in groups:
+        N = next(iter(targets[grp[0]].values())).shape[0]
+        parts = {s: [] for s in grp}
+        for b0 in range(0, N, bs):
+            dev = lambda s, k: torch.from_numpy(np.ascontiguousarray(targets[s][k][b0:b0 + bs])).to(device) if k in targets[s] else None  # noqa: E731
+            n = min(bs, N - b0)
+            arg = lambda k: [dev(s, k) for s in grp] if len(grp) == 2 else dev(grp[0], k)  # noqa: E731
+            init = [dev(s, 'init') if 'init' in targets[s] else MF.neutral_para(n, cam_scale, device) for s in grp]
+            w = dict(weights or {})
+            for k, t in (('w_verts', 'verts'), ('w_joints', 'joints'), ('w_uv', 'joint_uv')):
+                if not any(t in targets[s] for s in grp):
+                    w[k] = 0.0
+                else:
+                    w.setdefault(k, MF.DEFAULT_WEIGHTS[k])
+            r = MF.fit_mano([tables[s] for s in grp] if len(grp) == 2 else tables[grp[0]], init if len(grp) == 2 else init[0], arg('verts'), arg('joints'),
+                            arg('joints_conf'), arg('joint_uv'), arg('uv_conf'), iters=iters, lr=lr, weights=w)
+            for h, s in enumerate(grp):
+                parts[s].append({k: (getattr(r, k)[h] if len(grp) == 2 else getattr(r, k)).cpu().numpy() for k in ('para', 'verts', 'joints', 'joint_uv', 'mse_before',
+                                                                                                                    'mse_after', 'status')})
+        for s in grp:
+            out[s] = {k: np.concatenate([p[k] for p in parts[s]]) for k in parts[s][0]}
+    return out
+
+
+def main(argv=None):
+    import argparse
+
+    import torch
+
+    from . import checkpoint_weights
+    ap = argparse.ArgumentParser(description='fit MANO parameters (the 64-vector of pd_mano_para_*) to meshes, 3-D joints and 2-D keypoints on the GPU')
+    ap.add_argument('--model', type=str, required=True, help='a DIR checkpoint: its MANO tables are used')
+    ap.add_argument('--ema', action='store_true')
+    ap.add_argument('--targets', type=str, required=True, help='T.npz: verts_/joints_/joints_conf_/joint_uv_/uv_conf_/init_<side>')
+    ap.add_argument('--out', type=str, required=True)
+    ap.add_argument('--iters', type=int, default=200)
+    ap.add_argument('--lr', type=float, default=0.1, help='the learning rate of every group (not tuned on real data)')
+    for g in ('root', 'pca', 'betas', 'cam'):
+        ap.add_argument('--lr_' + g, type=float, default=None, help='the learning rate of this group instead of --lr (0 freezes it)')
+    ap.add_argument('--bs', type=int, default=256)
+    ap.add_argument('--center', type=int, default=0, help='the joint 3-D targets are relative to (-1: none)')
+    ap.add_argument('--cam_scale', type=float, default=1.0, help='the camera scale of the cold start')
+    for k, d in (('w_verts', None), ('w_joints', None), ('w_uv', None), ('w_pca', 0.0), ('w_beta', 0.0), ('w_init', 0.0)):
+        ap.add_argument('--' + k, type=float, default=d)
+    opt = ap.parse_args(argv)
+    if opt.bs < 1 or opt.iters < 0 or not -1 <= opt.center < 21:
+        ap.error('--bs must be at least 1, --iters at least 0 and --center in -1 .. 20')
+    with np.load(opt.targets) as f:
+        targets = read_targets(f)
+    state = checkpoint_weights(torch.load(opt.model, map_location='cpu', weights_only=False), opt.ema, opt.model)
+    tables, keep = tables_from_checkpoint(state, opt.center)
+    lr = {g: (getattr(opt, 'lr_' + g) if getattr(opt, 'lr_' + g) is not None else opt.lr) for g in ('root', 'pca', 'betas', 'cam')}
+    weights = {k: getattr(opt, k) for k in ('w_verts', 'w_joints', 'w_uv', 'w_pca', 'w_beta', 'w_init') if getattr(opt, k) is not None}
+    t0 = time.perf_counter()
+    res = fit_targets(tables, targets, opt.iters, lr, weights, opt.bs, opt.cam_scale)
+    torch.cuda.synchronize()
+    sec = time.perf_counter() - t0
+    np.savez(opt.out, **{'%s_%s' % (k, s): v for s, d in res.items() for k, v in d.items()})
+    n = sum(d['para'].shape[0] for d in res.values())
+    for s, d in res.items():
+        with np.errstate(invalid='ignore'):
+            print('%s: %d hands, mean squared residual (verts, joints, joint_uv) %s -> %s, %d with a status' % (
+                s, d['para'].shape[0], d['mse_before'].mean(0).tolist(), d['mse_after'].mean(0).tolist(), int((d['status'] != 0).sum())))
+    print('%d hands in %.2f s' % (n, sec))
+    return n
+
+
+if __name__ == '__main__':
+    main()

@@ -4,6 +4,7 @@ the GPU) -> DirEngine.forward -> predictions in FRAME pixels.
     python -m dir_amd.apps.predict --model CKPT --input DIR|FILES --out DIR [--boxes boxes.json] [--track] [--ratio 0.8] [--bs 32]
                                    [--stage 2] [--dtype f16|bf16|f32] [--workers 8] [--pictures] [--joints] [--obj] [--antialias]
                                    [--smooth] [--smooth_box] [--fps 30] [--min_cutoff 1.0] [--beta 0.007] [--d_cutoff 1.0]
+                                   [--keypoints FILE] [--refine_iters 50] [--refine_lr 0.01] [--refine_prior 1e-3]
 
 Input: image files (jpg / jpeg / png / bmp) in natural name order, decoded to BGR on the host with Pillow by worker threads that never
 touch the GPU, packed into FrameBatches of at most --bs images.  --boxes: a JSON object {"name": [x0, y0, x1, y1]} keyed by file name (or
@@ -33,6 +34,16 @@ of the raw and of the filtered values, and a line before the last one prints the
 of its own before the next crop is made, on the device; a first box and a held box are unchanged.  This changes the crops, and with them
 every prediction after frame 1.  These flags without --track are an error.
 
+--keypoints FILE: 2-D keypoints from an external detector or an annotator, a JSON object {"name": {"left": [[x, y, conf] x 21], "right": ...}}
+keyed like --boxes; frame pixels, in the joint order of pd_joint_uv_*; a hand, or an image, may be absent, and a confidence of 0 drops a keypoint.
+After the forward the stage's pd_mano_para_* are refined against them by dir_mano_fit (utils/mano_fit.py: --refine_iters Adam steps at
+--refine_lr inside one launch, no host read): the keypoints go into crop coordinates (from_frame_pixels, rounded once), only the 2-D term and
+the pull towards the network's own parameters (w_init = --refine_prior) are used, and the betas are frozen.  left / right then hold the fit's
+meshes, joints, 2-D joints and cameras, "unrefined" what they are without the flag, bit for bit; a hand without a usable keypoint, or whose fit
+reports a non-finite input or step, keeps the network's values ("refined_hands").  --track takes its next box from the refined meshes and
+--smooth filters the refined values.  The defaults are NOT tuned on real keypoints; Adam's steps are lr-sized whatever the residual, so
+keypoints the network already meets to a fraction of a pixel come back jittered at that scale.  Without --keypoints nothing changes.
+
 Output per image, <out>/<stem>.json (in --track with sub-directories <out>/<sequence>/<stem>.json):
   image, width, height   the file and its size
   box                    the tight box the crop was made from (null for a frame whose crop was tracked or held)
@@ -45,6 +56,8 @@ Output per image, <out>/<stem>.json (in --track with sub-directories <out>/<sequ
   antialiased            only with --antialias: true where the crop was made with the anti-aliased rule (it shrinks the frame)
   smoothed, raw          only with --smooth: true, and {"left", "right", "offset"} as they are without the flag
   box_smoothed           only with --smooth_box: true where this frame's matrix went through the box filter
+  refined, refined_hands, unrefined   only with --keypoints: true, {"left": bool, "right": bool} (which hands the fit replaced), and
+                         {"left", "right"} as they are without the flag
 --pictures: <stem>.png, crop | overlay side by side as apps.visualize writes them (--joints as there).  --obj: <stem>.obj, both hands
 placed as vis_utils.prediction_camera places them, faces from the checkpoint.  The last line printed is "N images in T s: R images/s".
 """
@@ -108,6 +121,29 @@ def box_for(boxes, path, height, width):
     return [0.0, 0.0, float(width - 1), float(height - 1)]
 
 
+def keypoints_for(kps, path):
+    """the entry of --keypoints for a file (keys as box_for's: directory/name, directory/stem, name, stem), or None"""
+    name = os.path.basename(path)
+    stem, seq = os.path.splitext(name)[0], os.path.basename(os.path.dirname(os.path.abspath(path)))
+    for k in (seq + '/' + name, seq + '/' + stem, name, stem):
+        if kps and k in kps:
+            return kps[k]
+    return None
+
+
+def keypoint_array(entries):
+    """[{"left": [[x, y, conf] x 21], "right": ...} or None per image] -> float32 [B,2,21,3]; an absent hand or image: confidence 0"""
+    out = np.zeros((len(entries), 2, 21, 3), np.float32)
+    for i, e in enumerate(entries):
+        for h, s in enumerate(SIDES):
+            if e is not None and e.get(s) is not None:
+                a = np.asarray(e[s], np.float32)
+                if a.shape != (21, 3):
+                    raise ValueError('predict: the keypoints of a hand must be [[x, y, conf] x 21], got shape %s' % (list(a.shape),))
+                out[i, h] = a
+    return out
+
+
 class Tracker(object):
     """The crop of every frame of one or more sequences that advance in lockstep.
 
@@ -125,9 +161,14 @@ class Tracker(object):
     smooth (True, or a dict of utils.smooth.OneEuro's parameters; needs track): after every forward the stage goes through a
     PredictionSmoother sized by the first step; `smoothed` is its result (frame space) and drawn(outs) the stage dict to draw.  smooth_box
     (likewise): the next matrices go through smooth_matrices before the next crop; `box_smoothed` int32 [B] says which of the current
-    matrices did.  Neither reads anything back."""
+    matrices did.  Neither reads anything back.
 
-    def __init__(self, eng, ratio=0.8, stage=2, size=SIZE, track=True, antialias=False, smooth=None, smooth_box=None):
+    refine (a dict with iters, lr, prior): step(..., keypoints=float32 [B,2,21,3] frame pixels | confidence) refines the stage's
+    pd_mano_para_* against them with utils.mano_fit.fit_mano right after the forward, on the device: the stage dict of `outs` is then the
+    refined one (tracking, smoothing and drawing go on from it), `unrefined` the network's own and `refined_hands` bool [B,2] which hands the
+    fit replaced."""
+
+    def __init__(self, eng, ratio=0.8, stage=2, size=SIZE, track=True, antialias=False, smooth=None, smooth_box=None, refine=None):
         self.eng, self.ratio, self.stage, self.size, self.track = eng, float(ratio), int(stage), int(size), bool(track)
         self.antialias = bool(antialias)
         self.M = self.valid = self.tracked = self.area = None
@@ -136,12 +177,48 @@ class Tracker(object):
         if (self.smooth is not None or self.smooth_box is not None) and not self.track:
             raise ValueError('Tracker: smooth and smooth_box need track=True')
         self.smoother = self.box_filter = self.smoothed = self.box_smoothed = self._box_updated = None
+        self.refine = None if refine is None else dict(refine)
+        self.unrefined = self.refined_hands = None
+
+    def _stage_tables(self):
+        e = self.eng
+        return e.init_mano if self.stage == 0 else (e.stage4, e.stage3)[self.stage - 1].mano if self.stage < 3 else e.stages_x[self.stage - 3].mano
+
+    def _refine(self, o, keypoints):
+        """the stage dict with the hands that have keypoints replaced by their fit (2-D term + prior, betas frozen)"""
+        import torch
+
+        from ..utils import crop as CR
+        from ..utils import mano_fit as MF
+        dev, B = self.eng.device, o['pd_mano_para_left'].shape[0]
+        kp = torch.as_tensor(np.zeros((B, 2, 21, 3), np.float32) if keypoints is None else np.asarray(keypoints, np.float32).reshape(B, 2, 21, 3)).to(dev)
+        uv, conf = [], []
+        for h in range(2):
+            c = kp[:, h, :, 2]
+            c = torch.where(torch.isfinite(c) & (c > 0) & (self.valid[:, None] > 0), c, torch.zeros((), device=dev))
+            u = CR.from_frame_pixels(kp[:, h, :, :2], self.M, self.size).float()              # rounded once
+            uv.append(torch.where((c > 0)[..., None], u, torch.zeros((), device=dev)).contiguous())
+            conf.append(c.contiguous())
+        lr = float(self.refine.get('lr', 0.01))
+        res = MF.fit_mano(list(self._stage_tables()), [o['pd_mano_para_left'], o['pd_mano_para_right']], joint_uv=uv, uv_conf=conf,
+                          iters=int(self.refine.get('iters', 50)), lr={'root': lr, 'pca': lr, 'betas': 0.0, 'cam': lr},
+                          weights={'w_uv': 1.0, 'w_init': float(self.refine.get('prior', 1e-3))})
+        new, taken = dict(o), []
+        for h, s in enumerate(SIDES):
+            take = (conf[h] > 0).any(1) & ((res.status[h] & 6) == 0)
+            taken.append(take)
+            para = torch.where(take[:, None], res.para[h], o['pd_mano_para_' + s])
+            new['pd_mano_para_' + s], new['pd_proj_' + s] = para, para[:, 61:64]
+            for k, r in (('pd_mesh_xyz_', res.verts[h]), ('pd_joint_xyz_', res.joints[h]), ('pd_joint_uv_', res.joint_uv[h])):
+                new[k + s] = torch.where(take[:, None, None], r.to(o[k + s].dtype), o[k + s])
+        self.refined_hands = torch.stack(taken, 1)
+        return new
 
     def drawn(self, outs):
         """the stage dict to draw: the smoothed prediction in the current crop, or the stage itself"""
         return self.smoother.crop_stage() if self.smoother is not None else outs[self.stage]
 
-    def step(self, batch, boxes=None):
+    def step(self, batch, boxes=None, keypoints=None):
         import torch
 
         from ..utils import crop as CR
@@ -167,7 +244,12 @@ class Tracker(object):
         else:
             crops, status = CR.crop_frames(batch, self.M, self.valid, self.size, return_status=True)
         self.valid = self.valid * (status == 0).to(torch.int32)            # a crop the kernel refused is black: the image is not valid
-        outs = self.eng.forward(crops, want_proj_feat=False)
+        if self.refine is None:
+            outs = self.eng.forward(crops, want_proj_feat=False)
+        else:
+            outs = list(self.eng.forward(crops, want_proj_feat=False, want_para=True))
+            self.unrefined = outs[self.stage]
+            outs[self.stage] = self._refine(outs[self.stage], keypoints)
         if self.track:
             M_next, ok = CR.crop_matrices_from_meshes(outs[self.stage], self.M, self.ratio, self.size)
             if self.smooth_box is not None:
@@ -199,6 +281,16 @@ def _records(paths, batch, boxes_used, tr, outs, stage, keep_stage):
     if keep_stage:
         for k in ('pd_mesh_xyz_left', 'pd_mesh_xyz_right', 'pd_proj_left', 'pd_proj_right', 'pd_joint_uv_left', 'pd_joint_uv_right'):
             t[k] = o[k].float()
+    un = tr.unrefined if tr.refine is not None else None
+    if un is not None:
+        t['refined_hands'] = tr.refined_hands
+        for s in SIDES:
+            t['u_px_' + s] = CR.to_frame_pixels(un['pd_joint_uv_' + s].float(), M, tr.size)
+            t['u_xyz_' + s] = un['pd_joint_xyz_' + s].float()
+            t['u_sc_' + s], t['u_tr_' + s] = CR.frame_camera(un['pd_proj_' + s].float(), M, tr.size)
+        if keep_stage:
+            for k in ('pd_mesh_xyz_left', 'pd_mesh_xyz_right', 'pd_proj_left', 'pd_proj_right', 'pd_joint_uv_left', 'pd_joint_uv_right'):
+                t['u_' + k] = un[k].float()
     fr = tr.smoothed if tr.smooth is not None else None
     if fr is not None:
         t['s_offset'] = fr['offset']
@@ -222,6 +314,11 @@ def _records(paths, batch, boxes_used, tr, outs, stage, keep_stage):
             r[s] = {'joints_px': num(h['px_' + s][j].tolist()), 'joints_xyz': num(h['xyz_' + s][j].tolist()),
                     'camera_px': {'scale': num(float(h['sc_' + s][j])), 'trans': num(h['tr_' + s][j].tolist())}}
         r['offset'] = num(h['offset'][j].reshape(-1).tolist())
+        if un is not None:
+            r['unrefined'] = {s: {'joints_px': num(h['u_px_' + s][j].tolist()), 'joints_xyz': num(h['u_xyz_' + s][j].tolist()),
+                                  'camera_px': {'scale': num(float(h['u_sc_' + s][j])), 'trans': num(h['u_tr_' + s][j].tolist())}} for s in SIDES}
+            r['refined'] = True
+            r['refined_hands'] = {s: bool(h['refined_hands'][j][i]) for i, s in enumerate(SIDES)}
         if fr is not None:                                                # the fields above are today's: they move to "raw"
             r['raw'] = {k: r[k] for k in SIDES + ('offset',)}
             for s in SIDES:
@@ -235,6 +332,8 @@ def _records(paths, batch, boxes_used, tr, outs, stage, keep_stage):
             r['antialiased'] = bool(h['area'][j])
         if keep_stage:
             r['stage'] = {k: h[k][j] for k in h if k.startswith('pd_')}
+            if un is not None:
+                r['stage_unrefined'] = {k[2:]: h[k][j] for k in h if k.startswith('u_pd_')}
             if fr is not None:
                 r['stage_smoothed'] = {k[2:]: h[k][j] for k in h if k.startswith('s_pd_')}
         recs.append(r)
@@ -262,15 +361,19 @@ def lockstep_groups(seqs, bs):
     return [[[(g0 + i, item) for i, item in st] for st in lockstep(seqs[g0:g0 + bs])] for g0 in range(0, len(seqs), bs)]
 
 
-def _walk(eng, steps, load, names, box_of, ratio, stage, track, keep_stage, antialias=False, smooth=None, smooth_box=None):
+def _walk(eng, steps, load, names, box_of, ratio, stage, track, keep_stage, antialias=False, smooth=None, smooth_box=None, refine=None, kp_of=None):
     """the one loop: per step FrameBatch -> Tracker.step -> records.  load(k) -> the decoded frames of step k; box_of(entry, h, w) -> the
-    box of a step entry.  Yields (entries, records, crops, outs, tracker) with the device tensors of that step."""
+    box of a step entry; kp_of(step index, entry) -> its keypoints entry or None (with refine).  Yields (entries, records, crops, outs, tracker)
+    with the device tensors of that step."""
     from ..utils import crop as CR
-    tr = Tracker(eng, ratio, stage, track=track, antialias=antialias, smooth=smooth, smooth_box=smooth_box)
+    tr = Tracker(eng, ratio, stage, track=track, antialias=antialias, smooth=smooth, smooth_box=smooth_box, refine=refine)
     for k, st in enumerate(steps):
         batch = CR.FrameBatch(load(k))
         used = [box_of(e, h, w) for e, (h, w) in zip(st, batch.sizes)] if (not track or k == 0) else None
-        crops, outs = tr.step(batch, used)
+        if refine is not None:
+            crops, outs = tr.step(batch, used, keypoint_array([kp_of(k, e) for e in st]))
+        else:
+            crops, outs = tr.step(batch, used)
         yield st, _records([names(e) for e in st], batch, used, tr, outs, stage, keep_stage), crops, outs, tr
 
 
@@ -302,7 +405,7 @@ def jitter_summary(jitters):
 
 
 def predict(eng, frames, boxes=None, ratio=0.8, stage=2, bs=32, track=False, keep_stage=False, keep_crops=False, antialias=False, smooth=None,
-            smooth_box=None, return_jitter=False):
+            smooth_box=None, return_jitter=False, keypoints=None, refine_iters=50, refine_lr=0.01, refine_prior=1e-3):
     """The loop behind the command, on decoded frames.
 
     frames: without `track` a list of uint8 BGR arrays [H,W,3] of any sizes, taken `bs` at a time; with `track` a list of sequences (each
@@ -314,7 +417,15 @@ def predict(eng, frames, boxes=None, ratio=0.8, stage=2, bs=32, track=False, kee
     shrinks its frame; every record then has 'antialiased'.
     smooth / smooth_box (with `track`; True or a dict of utils.smooth.OneEuro's parameters): Tracker's.  With smooth a record's left, right
     and offset are filtered, 'raw' holds the unfiltered ones, and keep_stage adds 'stage_smoothed' (PredictionSmoother.crop_stage);
-    return_jitter -> (records, [sequence_jitter per sequence])."""
+    return_jitter -> (records, [sequence_jitter per sequence]).
+    keypoints: one {"left": [[x, y, conf] x 21], "right": ...} or None per image (with `track` one such list per sequence), frame pixels: the
+    stage is refined against them (the module docstring's --keypoints; refine_iters, refine_lr, refine_prior); every record then has
+    'unrefined', 'refined' and 'refined_hands', and keep_stage adds 'stage_unrefined'.  None: nothing changes."""
+    refine = None if keypoints is None else {'iters': refine_iters, 'lr': refine_lr, 'prior': refine_prior}
+
+    def kp_of(k, e):
+        entry = keypoints[e[0]]
+        return (entry[k] if k < len(entry) else None) if track and entry is not None else entry
     if (smooth or smooth_box) and not track:
         raise ValueError('predict: smooth and smooth_box need track=True')
     if return_jitter and not smooth:
@@ -332,7 +443,7 @@ def predict(eng, frames, boxes=None, ratio=0.8, stage=2, bs=32, track=False, kee
     for steps in groups:
         tr = None
         for st, recs, crops, outs, tr in _walk(eng, steps, lambda k: [f for _, f in steps[k]], lambda e: str(e[0]), box_of, ratio, stage, track,
-                                                keep_stage, antialias, smooth, smooth_box):
+                                                keep_stage, antialias, smooth, smooth_box, refine, kp_of):
             ch = crops.cpu().numpy() if keep_crops else None
             for j, ((i, _), r) in enumerate(zip(st, recs)):
                 if keep_crops:
@@ -348,11 +459,12 @@ def predict(eng, frames, boxes=None, ratio=0.8, stage=2, bs=32, track=False, kee
 
 
 def run(eng, sequences, out_dir, boxes=None, ratio=0.8, stage=2, bs=32, track=False, workers=8, pictures=False, joints=False, obj=False,
-        renderer=None, faces=None, antialias=False, smooth=None, smooth_box=None, jitter_out=None):
+        renderer=None, faces=None, antialias=False, smooth=None, smooth_box=None, jitter_out=None, keypoints=None, refine=None):
     """files -> files.  sequences: [[paths]] (one list without `track`).  -> (images, seconds, seconds of them spent waiting for decoded
     frames).  Two steps are decoded ahead of the GPU by at most 16 threads; the files are written by 8 more.  With `track`, more than `bs`
     sequences walk `bs` at a time, so that no batch holds more than `bs` images.  smooth / smooth_box: Tracker's; with smooth the pictures
-    and OBJs show the filtered prediction, every sequence gets a jitter.json, and a list given as jitter_out receives their contents."""
+    and OBJs show the filtered prediction, every sequence gets a jitter.json, and a list given as jitter_out receives their contents.
+    keypoints: the --keypoints object (keypoints_for's keys) with refine = {'iters', 'lr', 'prior'}: every stage is refined against them."""
     from concurrent.futures import ThreadPoolExecutor
 
     from ..utils import vis_utils as V
@@ -385,7 +497,8 @@ def run(eng, sequences, out_dir, boxes=None, ratio=0.8, stage=2, bs=32, track=Fa
                 return frames
             tr = None
             for st, recs, crops, outs, tr in _walk(eng, steps, load, lambda e: e[1], lambda e, h, w: box_for(boxes, e[1], h, w), ratio, stage, track,
-                                                    False, antialias, smooth, smooth_box):
+                                                    False, antialias, smooth, smooth_box, (refine or {}) if keypoints is not None else None,
+                                                    lambda k, e: keypoints_for(keypoints, e[1])):
                 shown = tr.drawn(outs) if pictures or obj else None
                 if pictures:
                     over = V.overlay_predictions(shown, crops, renderer)
@@ -443,6 +556,10 @@ def main(argv=None):
     ap.add_argument('--min_cutoff', type=float, default=None, help='One-Euro: the cutoff at rest, Hz (default 1.0, the paper\'s; not tuned on real video)')
     ap.add_argument('--beta', type=float, default=None, help='One-Euro: cutoff per speed, Hz per (mm/s or px/s) (default 0.007)')
     ap.add_argument('--d_cutoff', type=float, default=None, help='One-Euro: the cutoff of the speed estimate, Hz (default 1.0)')
+    ap.add_argument('--keypoints', type=str, default=None, help='JSON {"name": {"left": [[x, y, conf] x 21], "right": ...}}: 2-D keypoints in frame pixels the prediction is refined against')
+    ap.add_argument('--refine_iters', type=int, default=None, help='with --keypoints: Adam steps of the refinement (default 50; not tuned on real keypoints)')
+    ap.add_argument('--refine_lr', type=float, default=None, help='with --keypoints: their learning rate (default 0.01)')
+    ap.add_argument('--refine_prior', type=float, default=None, help="with --keypoints: the weight of the pull towards the network's own parameters (default 1e-3)")
     opt = ap.parse_args(argv)
     if opt.bs < 1:
         ap.error('--bs must be at least 1')
@@ -453,6 +570,11 @@ def main(argv=None):
         ap.error('--fps, --min_cutoff, --beta and --d_cutoff need --smooth or --smooth_box')
     if any(v <= 0 for k, v in params.items() if k != 'beta') or params.get('beta', 0.0) < 0:
         ap.error('--fps, --min_cutoff and --d_cutoff must be positive and --beta not negative')
+    rp = {k: getattr(opt, 'refine_' + k) for k in ('iters', 'lr', 'prior') if getattr(opt, 'refine_' + k) is not None}
+    if rp and not opt.keypoints:
+        ap.error('--refine_iters, --refine_lr and --refine_prior need --keypoints')
+    if rp.get('iters', 1) < 0 or rp.get('lr', 1.0) < 0 or rp.get('prior', 1.0) < 0:
+        ap.error('--refine_iters, --refine_lr and --refine_prior must not be negative')
     sequences = list_sequences(opt.input) if opt.track else [list_images(opt.input)]
     if not any(sequences):
         raise ValueError('predict: no image files (%s) in %s' % (' / '.join(EXTENSIONS), opt.input))
@@ -460,6 +582,10 @@ def main(argv=None):
     if opt.boxes:
         with open(opt.boxes) as f:
             boxes = json.load(f)
+    keypoints = None
+    if opt.keypoints:
+        with open(opt.keypoints) as f:
+            keypoints = json.load(f)
     state = torch.load(opt.model, map_location='cpu', weights_only=False)
     from . import checkpoint_weights
     state = checkpoint_weights(state, opt.ema, opt.model)
@@ -473,7 +599,7 @@ def main(argv=None):
                                                         device=eng.device)
     jitters = []
     n, sec, wait = run(eng, sequences, opt.out, boxes, opt.ratio, opt.stage, opt.bs, opt.track, opt.workers, opt.pictures, opt.joints, opt.obj,
-                       renderer, faces, opt.antialias, (params or True) if opt.smooth else None, (params or True) if opt.smooth_box else None, jitters)
+                       renderer, faces, opt.antialias, (params or True) if opt.smooth else None, (params or True) if opt.smooth_box else None, jitters, keypoints, rp)
     print('waited %.2f s of them for decoded frames' % wait)
     if opt.smooth:
         mm, px = jitter_summary(jitters)

@@ -1614,9 +1614,10 @@ class DirEngine(object):
     # ------------------------------------------------------------------------------------------ forward
     _flags = None
 
-    def forward(self, img, want_proj_feat=True, taps=None, reflection_flags=None):
+    def forward(self, img, want_proj_feat=True, taps=None, reflection_flags=None, want_para=False):
         """img: float32 NCHW [B,3,256,256] on the GPU.  Returns outs_list exactly like DIR.forward (models/dir.py:521-540);
         tensors are engine-owned buffers (valid until the next forward when run under a captured graph).
+        want_para: every stage dict also holds pd_mano_para_left / pd_mano_para_right [B,64] (what utils.mano_fit refines; pd_proj_* are views of them).
         reflection_flags: optional int32 tensor [3 (+ extra) stages, 2 hands, B]; an entry is set to 1 where the predicted 6D root rotation
         is a reflection (det < 0) -- where the reference's `assert` fires (rot6d.py:50).  The caller decides when to look (a host
         read); dir_amd.models.dir.DIR.forward does, and raises AssertionError like the reference."""
@@ -1624,12 +1625,12 @@ class DirEngine(object):
         self._flags = reflection_flags
         _TLS.no_out_split = taps is not None          # the taps are read as fp32 maps
         try:
-            return self._forward(img, want_proj_feat, taps)
+            return self._forward(img, want_proj_feat, taps, want_para)
         finally:
             self._flags = None
             _TLS.no_out_split = False
 
-    def _forward(self, img, want_proj_feat, taps):
+    def _forward(self, img, want_proj_feat, taps, want_para=False):
         if img.dtype == torch.uint8:     # decoded BGR frames [B,256,256,3]: the reference's normalisation runs inside the stem staging
             assert img.is_contiguous() and img.shape[1:] == (256, 256, 3)
         else:
@@ -1692,7 +1693,7 @@ class DirEngine(object):
         for o in [init, r4, r3] + extra:
             outs.append({k: o[k] for k in ('pd_joint_uv_left', 'pd_joint_uv_right', 'pd_mesh_xyz_left',
                                            'pd_mesh_xyz_right', 'pd_joint_xyz_left', 'pd_joint_xyz_right',
-                                           'pd_proj_left', 'pd_proj_right', 'pd_offset', 'pd_rel_joint')})
+                                           'pd_proj_left', 'pd_proj_right', 'pd_offset', 'pd_rel_joint') + (('pd_mano_para_left', 'pd_mano_para_right') if want_para else ())})
         outs.append({'dense': dense.permute(0, 3, 1, 2), 'seg': seg.permute(0, 3, 1, 2),
                      'proj_feat': (extra[-1] if extra else r3)['vis_img_feat']})
         return outs

@@ -320,3 +320,52 @@ def regress_backward(w_left, w_right, w_offset, tok, prev_para_left, prev_para_r
                                                  _capi.ptr(out['mano_right.weight']), _capi.ptr(out['mano_right.bias']), _capi.ptr(out['offset.weight']),
                                                  _capi.ptr(out['offset.bias']), _capi.ptr(out['tok']), B, _capi.stream_ptr()), 'dir_regress_backward')
     return out
+
+
+MANO_FIT_WEIGHTS = ('w_verts', 'w_joints', 'w_uv', 'w_pca', 'w_beta', 'w_init')
+MANO_FIT_GROUPS = ('root', 'pca', 'betas', 'cam')
+
+
+def mano_fit(tables_lr, init_lr, verts=None, joints=None, joints_conf=None, joint_uv=None, uv_conf=None, iters=200, lr=(0.1, 0.1, 0.1, 0.1),
+             weights=None, betas=(0.9, 0.999), eps=1e-8, anchor=None, state=None, outputs=True, para_out=None):
+    """dir_mano_fit (include/dir_hip.h, "MANO fitting").  tables_lr: list of _capi.ManoTables (1 or 2 hands); init_lr: list of fp32 [B,64]
+    contiguous GPU tensors; verts / joints / joints_conf / joint_uv / uv_conf / anchor / state / para_out: None, or lists with one tensor or None per
+    hand (state: float32 [B, MANO_FIT_STATE], updated in place; para_out may hold the init tensors themselves).  lr: four floats (root, pca, betas,
+    cam); weights: dict over MANO_FIT_WEIGHTS (missing = 0).  -> list per hand of dicts para, mse [B,6], status [B] (+ verts, joints, joint_uv
+    with outputs)."""
+    import ctypes as C
+    hands = len(init_lr)
+    assert hands in (1, 2) and len(tables_lr) == hands
+    B, dev = init_lr[0].shape[0], init_lr[0].device
+
+    def per_hand(ts, shape, what):
+        ts = [None] * hands if ts is None else list(ts)
+        assert len(ts) == hands
+        for t in ts:
+            if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape and t.device == dev):
+                raise _capi.DirHipError('mano_fit: %s must be a contiguous float32 %s tensor on %s' % (what, list(shape), dev))
+        _capi.require_cuda(*ts)
+        return ts
+    init = per_hand(init_lr, (B, 64), 'init')
+    tv, tj, cj = per_hand(verts, (B, 778, 3), 'verts'), per_hand(joints, (B, 21, 3), 'joints'), per_hand(joints_conf, (B, 21), 'joints_conf')
+    tu, cu = per_hand(joint_uv, (B, 21, 2), 'joint_uv'), per_hand(uv_conf, (B, 21), 'uv_conf')
+    an, st, po = per_hand(anchor, (B, 64), 'anchor'), per_hand(state, (B, _capi.MANO_FIT_STATE), 'state'), per_hand(para_out, (B, 64), 'para_out')
+    w = dict(weights or {})
+    if set(w) - set(MANO_FIT_WEIGHTS):
+        raise ValueError('mano_fit: unknown weights %s' % sorted(set(w) - set(MANO_FIT_WEIGHTS)))
+    opts = _capi.ManoFitOpts(*[float(w.get(k, 0.0)) for k in MANO_FIT_WEIGHTS], (C.c_float * 4)(*[float(v) for v in lr]), float(betas[0]), float(betas[1]),
+                             float(eps), int(iters))
+    res, hs = [], []
+    for h in range(hands):
+        r = {'para': po[h] if po[h] is not None else torch.empty(B, 64, device=dev), 'mse': torch.empty(B, 6, device=dev),
+             'status': torch.empty(B, dtype=torch.int32, device=dev)}
+        if outputs:
+            r.update(verts=torch.empty(B, 778, 3, device=dev), joints=torch.empty(B, 21, 3, device=dev), joint_uv=torch.empty(B, 21, 2, device=dev))
+        P = _capi.ptr
+        hs.append(_capi.ManoFitHand(init[h].data_ptr(), P(an[h]), r['para'].data_ptr(), P(tv[h]), P(tj[h]), P(cj[h]), P(tu[h]), P(cu[h]),
+                                    P(r.get('verts')), P(r.get('joints')), P(r.get('joint_uv')), r['mse'].data_ptr(), r['status'].data_ptr(), P(st[h])))
+        res.append(r)
+    with torch.cuda.device(dev):
+        _capi.check(_capi.lib().dir_mano_fit((_capi.ManoTables * hands)(*tables_lr), (_capi.ManoFitHand * hands)(*hs), C.byref(opts), hands, B,
+                                             _capi.stream_ptr()), 'dir_mano_fit')
+    return res

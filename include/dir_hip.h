@@ -29,7 +29,7 @@ extern "C" {
 #define DIR_E_LAUNCH (-2)   /* hipLaunchKernel / HIP runtime error          */
 #define DIR_E_NODEVICE (-3) /* no gfx950 device visible                     */
 
-#define DIR_ABI_VERSION 51
+#define DIR_ABI_VERSION 52
 
 int dir_abi_version(void);
 const char* dir_last_error(void);
@@ -118,6 +118,75 @@ int dir_mano_backward_pair(const dir_mano_tables* tables_lr_host, const float* c
                            const float* const* g_joint_uv_lr_host, const float* const* g_mesh_uv_lr_host,
                            float* const* g_pose_lr_host, int g_pose_stride, float* const* g_betas_lr_host, int g_betas_stride,
                            float* const* g_cam_lr_host, int g_cam_stride, int hands, int B, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * MANO fitting (ABI 52; nothing in the reference): dir_mano_forward run the other way.  Per (sample, hand) the 64-vector p = pose 51 (6D root |
+ * 45 PCA) | betas 10 | cam 3 -- the layout of pd_mano_para_* and of dir_mano_backward_pair -- is moved by `iters` Adam steps down
+ *
+ *   E(p) = w_verts  / 778 * sum_v       |V_v - V*_v|^2
+ *        + w_joints / 21  * sum_j c_j   |J_j - J*_j|^2
+ *        + w_uv     / 21  * sum_j d_j   |U_j - U*_j|^2
+ *        + w_pca * |p[6:51]|^2 + w_beta * |p[51:61]|^2 + w_init * |p - a|^2
+ *
+ * V(p) [778,3], J(p) [21,3], U(p) [21,2] are dir_mano_forward's verts, joints and joint_uv for the given tables (center_idx, side and root_palm as
+ * the caller set them: 3-D targets are relative to the same joint; there is no translation variable).  a = `anchor`, or p0 where it is NULL.
+ * A NULL target drops its term; NULL confidences are all 1.  A target whose confidence is not > 0 is selected out, never multiplied by 0: it
+ * may hold NaN (a missing keypoint).
+ *
+ * One iteration, in this order, fp32 throughout (one launch runs all of them; one 256-thread workgroup per (sample, hand) keeps the hand in LDS):
+ *   1. the forward at p, operation for operation dir_mano_forward's;
+ *   2. the cotangents gV = k_v (V - V*), gJ = (k_j c_j) (J_j - J*_j), gU = (k_uv d_j) (U_j - U*_j), 0 where selected out, with
+ *      k_v = 2 w_verts / 778, k_j = 2 w_joints / 21, k_uv = 2 w_uv / 21 formed in double on the host and rounded to float once;
+ *   3. g = dir_mano_backward_pair's gradient for these cotangents (same operations; 64-lane sums on DPP row operations, fixed order; with
+ *      root_palm, which that entry point rejects, joint 0 = (v95 + v22) / 2 hands half its gradient to each of the two vertices);
+ *   4. g[6:51] += (2 w_pca) p, then g[51:61] += (2 w_beta) p, then g += (2 w_init) (p - a), each product and sum rounded (no FMA contraction);
+ *   5. Adam, step t = t0 + 1 .. t0 + iters, per component of group G (root 0:6, pca 6:51, betas 51:61, cam 61:64), no FMA contraction:
+ *        m = b1 * m + (1 - b1) * g            v = b2 * v + (1 - b2) * (g * g)
+ *        P1 = P1 * b1, P2 = P2 * b2           (running fp32 products b1^t, b2^t, 1 at t = 0: the bias corrections are 1 - P1 and 1 - P2)
+ *        p = p - (lr_G * (m / (1 - P1))) / (sqrt(v / (1 - P2)) + eps)
+ *      a group with lr_G == 0 keeps its components bit for bit (m and v still move).
+ * The iteration count is fixed: no early stop, no host read, no data-dependent bound (one exception: status bit 2 below ends the row's loop).
+ *
+ * status (int32 per row, optional):
+ *   bit 0  the final iterate's 6D root is a reflection (flags_out's meaning in dir_mano_forward);
+ *   bit 1  p0 or `anchor` is non-finite, or a target in use (term present and confidence > 0; the confidence included) is non-finite: the row
+ *          passes through -- p_out = p0 bit for bit, its state is untouched, verts / joints / joint_uv are the forward at p0 and mse is 0 (all of
+ *          them 0 where p0 itself is non-finite);
+ *   bit 2  a step gave a non-finite component of p, m or v: that step is not taken, the iterate before it (the last finite one) is returned with
+ *          its state, and the row's loop ends there.
+ *
+ * mse [B,6] (optional): the unweighted mean squared residuals (verts, joints, joint_uv) at p0, then at the returned p:
+ *   sum_v |V_v - V*_v|^2 / 778, sum_{c_j > 0} |J_j - J*_j|^2 / #{c_j > 0}, the same for U; 0 where the term is absent or nothing is selected.
+ * state [B, DIR_MANO_FIT_STATE] (optional, in and out): m [64] | v [64] | P1 | P2 | t (the int32's bits) | 0.  All zeros is the fresh state.
+ *   With it (and `anchor` held fixed), iters = a followed by iters = b equals iters = a + b bit for bit.
+ * p_out may alias p0.  verts [B,778,3], joints [B,21,3], joint_uv [B,21,2] (optional): V, J, U at the returned p.
+ * Every reduction runs in a fixed order, no atomics, no workspace: a row gives the same bits in any slot of any batch and in either hand slot. */
+#define DIR_MANO_FIT_STATE 132
+typedef struct dir_mano_fit_hand {
+    const float* p0;          /* [B,64] start                                             */
+    const float* anchor;      /* [B,64] centre of the w_init term, or NULL = p0           */
+    float* p_out;             /* [B,64] fitted parameters (may alias p0)                   */
+    const float* verts_t;     /* V* [B,778,3] or NULL                                      */
+    const float* joints_t;    /* J* [B,21,3] or NULL                                       */
+    const float* joints_conf; /* c  [B,21] or NULL (= 1)                                   */
+    const float* uv_t;        /* U* [B,21,2] or NULL                                       */
+    const float* uv_conf;     /* d  [B,21] or NULL (= 1)                                   */
+    float* verts;             /* optional outputs at the returned p                        */
+    float* joints;
+    float* joint_uv;
+    float* mse;               /* [B,6] or NULL                                             */
+    int32_t* status;          /* [B] or NULL                                               */
+    float* state;             /* [B,DIR_MANO_FIT_STATE] in and out, or NULL                */
+} dir_mano_fit_hand;
+typedef struct dir_mano_fit_opts {
+    float w_verts, w_joints, w_uv, w_pca, w_beta, w_init;
+    float lr[4];              /* root, pca, betas, cam                                      */
+    float b1, b2, eps;        /* 0.9, 0.999, 1e-8 are the defaults of the Python callers    */
+    int32_t iters;
+} dir_mano_fit_opts;
+/* tables_host / hands_host: HOST arrays of `hands` (1 or 2) entries; grid = B x hands.  Enqueued on `stream`, graph-capture safe. */
+int dir_mano_fit(const dir_mano_tables* tables_host, const dir_mano_fit_hand* hands_host, const dir_mano_fit_opts* opts_host,
+                 int hands, int B, void* stream);
 
 /* Backward of RegressorOffset's three Linears (models/dir.py:339-351).  w_left / w_right [64][1408], w_offset [3][2691]: the
  * nn.Linear weights in their own layout; tok [B,42,64] = the STE head output (tokens 0..20 left); prev_* the previous stage's
