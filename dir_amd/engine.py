@@ -19,23 +19,35 @@ import torch
 
 from . import _capi
 from ._capi import CONV_PRE_RELU, CONV_RELU, DT_BF16, DT_F16, DT_F16X1, DT_F16X1P, DT_F16X3, DT_F16X3P, DT_F32, ConvDesc
+from .packing import pack_as_weights, pack_stream_weights, pack_tail_stream      # noqa: F401  (re-exported: tests and tools take them from here)
 
 F32 = torch.float32
 IMAGENET_MEAN = (C.c_float * 3)(0.485, 0.456, 0.406)      # apps/eval.py:49-50
 IMAGENET_STD = (C.c_float * 3)(0.229, 0.224, 0.225)
 # Live per-launch measurement: set _capi.PROFILE to a list and every library call is bracketed by HIP events and recorded with the
 # kernel names it launched plus the algorithmic work announced here with _capi.annotate() (bench.py roofline, DirEngine.autotune).
-_TLS = threading.local()      # .variant: DIR_CONV_VARIANT every conv of THIS thread is forced to (autotune); per thread, not global
+class _ThreadState(threading.local):
+    """per-thread switches of the plan; the class attributes are what a thread sees before it sets anything"""
+    variant = None          # DIR_CONV_VARIANT every conv of THIS thread is forced to (autotune); per thread, not global
+    arith = None            # 'f16x3' | 'f16' while a DirEngine packs its parameters (_packing_arith)
+    capture = None          # autotune_energy: list that collects every convolution call of a forward, replayable
+    capture_fused = None    # tools/energy_profile.py: the same for the fused bottleneck launches
+    calibrating = False     # DirEngine.calibrate: every f16-arithmetic convolution picks its in_scale from what it reads
+    no_out_split = False    # forward(taps=...): the taps are read as fp32 maps, no pre-split hand-over
 
 
-def _forced_variant():
-    return getattr(_TLS, 'variant', None)
+_TLS = _ThreadState()
+
+
+def _variant_for(op, B):
+    """DIR_CONV_VARIANT code of one launch of `op` at batch size B: the variant forced on this thread (autotune), else the op's tuned one"""
+    return _TLS.variant if _TLS.variant is not None else op.variant.get(B, 0)
 
 
 def _packing_arith():
     """'f16x3' while a DirEngine(dtype=float32, arith='f16x3') packs its parameters (per thread): every fp32 convolution built meanwhile
     takes the split-precision arithmetic (include/dir_hip.h: DIR_DT_F16X3), else None"""
-    return getattr(_TLS, 'arith', None)
+    return _TLS.arith
 
 
 def _ann(family, flops, nbytes, shape):
@@ -78,45 +90,6 @@ STREAM_VARIANTS = (STREAM_VARIANT, STREAM64_VARIANT, STREAM32_VARIANT, STREAMP_V
 AS_VARIANTS = {25: (2, 2), 26: (2, 4), 27: (4, 2), 28: (1, 2)}
 
 
-def pack_as_weights(w_ohwi, A):
-    """dir_conv2d_as_forward's weight stream (include/dir_hip.h) from W [Cout][kh][kw][Cin] (16-bit): [Cout / (128 A)][4 waves][kh kw Cin / 64 steps]
-    [4 k-steps][A][64 lanes][8], step = (64-channel slab) * (kh kw) + tap -- every wave's MFMA A fragments in the order it consumes them, with the
-    k-slot assignment of conv.hip's MFMAs (lanes 0-31: channels 8 ks .. + 8 of the slab, lanes 32-63: 32 + 8 ks .. + 8)."""
-    N, kh, kw, Cin = w_ohwi.shape
-    assert N % (128 * A) == 0 and Cin % 64 == 0
-    nt = kh * kw
-    dev = w_ohwi.device
-    w = w_ohwi.reshape(N, nt * Cin)
-    lane = torch.arange(64, device=dev)
-    l32, h = lane & 31, lane >> 5
-    e = torch.arange(8, device=dev)
-    g, wv, st, ks, cb = torch.meshgrid(torch.arange(N // (128 * A), device=dev), torch.arange(4, device=dev), torch.arange(nt * Cin // 64, device=dev),
-                                       torch.arange(4, device=dev), torch.arange(A, device=dev), indexing='ij')
-    row = (g * (128 * A) + (wv * A + cb) * 32)[..., None] + l32                       # [G,4,steps,4,A,64]
-    slab, tap = st // nt, st % nt
-    k0 = (tap * Cin + 64 * slab + 8 * ks)[..., None] + 32 * h
-    return w[row[..., None], k0[..., None] + e].contiguous()
-
-
-def pack_stream_weights(w_nk, dtype=torch.bfloat16):
-    """dir_conv1x1_stream_forward's weight stream (include/dir_hip.h) from W [Cout, K] (K = Cin, or Cin + Cin2 for two sources):
-    bf16 [Cout/NWG][4 waves][K/64][4 k-steps][NCB][64 lanes][8]."""
-    out_dev = w_nk.device
-    w = w_nk.detach().float().cpu()
-    N, K = w.shape
-    assert N % 128 == 0 and K % 64 == 0
-    ncb = 2 if N % 256 == 0 else 1
-    dev = w.device
-    lane = torch.arange(64, device=dev)
-    l32, h = lane & 31, lane >> 5
-    e = torch.arange(8, device=dev)
-    g, wv, c, ks, cb = torch.meshgrid(torch.arange(N // (128 * ncb), device=dev), torch.arange(4, device=dev), torch.arange(K // 64, device=dev),
-                                      torch.arange(4, device=dev), torch.arange(ncb, device=dev), indexing='ij')
-    row = (g * (128 * ncb) + (wv * ncb + cb) * 32)[..., None] + l32                    # [G,4,nk,4,ncb,64]
-    k0 = (64 * c + 8 * ks)[..., None] + 32 * h            # the k-slot assignment of conv.hip's MFMAs (bit-identical sums)
-    return w[row[..., None], k0[..., None] + e].to(dtype).contiguous().to(out_dev)
-
-
 class ConvOp(object):
     """one dir_conv2d_forward call with packed parameters"""
     def __init__(self, w_oihw, dtype, stride=1, pad=0, scale=None, shift=None, relu=False, pre=None, pre_relu=False,
@@ -146,7 +119,6 @@ class ConvOp(object):
         self.split_consumer = None                         # f16 arithmetic modes: the ONE convolution reading this op's whole output (link_split)
         self.alg_k = self.kh * self.kw * self.cin          # reduction length the reference computes (stem: 147)
         self.variant = {}                                  # batch size -> DIR_CONV_VARIANT code chosen by DirEngine.autotune
-        self.split, self._ws = {}, {}                      # batch size -> split-K factor; (B, S, stream) -> workspace
         self._w_as = {}                                    # A -> the activation-stationary kernel's weight stream (pack_as_weights), packed on first use
         # streaming alternative for the HBM-bound 1x1 layers (dir_conv1x1_stream_forward), taken when autotune prefers it
         self.w_stream = None
@@ -181,7 +153,7 @@ class ConvOp(object):
     def __call__(self, x, out=None, out_coff=0, in_coff=0, residual=None, res_coff=0, bbox=None, _replay_split=None):
         B, H, W, cbuf = x.shape
         x_arg, in_coff_arg = x, in_coff
-        if self.arith is not None and getattr(_TLS, 'calibrating', False):
+        if self.arith is not None and _TLS.calibrating:
             self._calibrate([x[..., in_coff:in_coff + self.cin]] if self.in_cs_override is None else [x])
         ho = self.ho or (H + 2 * self.pad - self.kh) // self.stride + 1
         wo = self.wo or (W + 2 * self.pad - self.kw) // self.stride + 1
@@ -208,16 +180,16 @@ class ConvOp(object):
                      residual.shape[3] if residual is not None else 0, res_coff, self.kh, self.kw, self.stride, self.pad,
                      in_code, _dt(out.dtype), flags, self.ho, self.wo, self.in_scale)
         cons = self.split_consumer
-        write_split = (cons is not None and out_given is None and residual_ok and not getattr(_TLS, 'calibrating', False)
-                       and not getattr(_TLS, 'no_out_split', False) and ConvOp.OUT_SPLIT)
+        write_split = (cons is not None and out_given is None and residual_ok and not _TLS.calibrating
+                       and not _TLS.no_out_split and ConvOp.OUT_SPLIT)
         if _replay_split is not None:
             write_split = _replay_split
-        if getattr(_TLS, 'capture', None) is not None:       # autotune_energy: this call, replayable (same output buffer, same hand-over format)
+        if _TLS.capture is not None:       # autotune_energy: this call, replayable (same output buffer, same hand-over format)
             _TLS.capture.append((self, (x_arg,), dict(out=out, out_coff=out_coff, in_coff=in_coff_arg, residual=residual, res_coff=res_coff, bbox=bbox,
                                                   _replay_split=write_split)))
         if write_split:      # the only reader is the next convolution: write its pre-split operand instead of fp32 (same bytes, no split pass)
             d.out_split_scale = -cons.in_scale if cons.arith == 'f16' else cons.in_scale
-        v = _forced_variant() if _forced_variant() is not None else self.variant.get(B, self.variant.get(getattr(_TLS, 'parent_batch', None), 0))
+        v = _variant_for(self, B)
         d.flags |= (v & 0xff) << 8
         if _capi.PROFILE is not None:
             nbytes = (B * H * W * self.cin * x.element_size() + self.w.numel() * self.w.element_size()
@@ -243,15 +215,6 @@ class ConvOp(object):
                                                                _capi.ptr(self.shift), _capi.ptr(self.pre_scale), _capi.ptr(self.pre_shift),
                                                                _capi.ptr(out), _capi.stream_ptr()), 'dir_conv1x1_stream_forward')
             return out
-        S = self.splits(B, ho, wo) if (bbox is None and out.dtype in HALF and self.dtype in HALF) else 1
-        if S > 1 and (_forced_variant() in (None, 0)):
-            d.flags &= 0xff
-            ws = self._splitk_ws(d, S, B, x.device)
-            _capi.check(_capi.lib().dir_conv2d_splitk_forward(d, _capi.ptr(x), _capi.ptr(self.w), _capi.ptr(self.scale), _capi.ptr(self.shift),
-                                                              _capi.ptr(self.pre_scale), _capi.ptr(self.pre_shift), _capi.ptr(residual),
-                                                              _capi.ptr(out), S, _capi.ptr(ws), ws.numel(), _capi.stream_ptr()),
-                        'dir_conv2d_splitk_forward')
-            return out
         if bbox is not None:
             rc = _capi.lib().dir_conv2d_sparse_forward(d, _capi.ptr(x), _capi.ptr(self.w), _capi.ptr(self.scale),
                                                        _capi.ptr(self.shift), _capi.ptr(residual), _capi.ptr(out),
@@ -265,37 +228,6 @@ class ConvOp(object):
         if write_split:
             out._dir_split = True
         return out
-
-
-    # ---- split-K (dir_conv2d_splitk_forward) for layers whose M x Cout grid of 128x128 tiles covers at most half of the 256 CUs at
-    # this batch size (ResNet layer4 at 8x8, the decoder's 16x16 Residual blocks).  OFF by default: measured at B = 64
-    # (tools/bench_splitk.py) it wins only on the 2304 -> 128 pre-activation 1x1 (46 -> 39 us) and ties on layer4's 3x3 (36 -> 34 us); every
-    # other candidate is slower than its best tiled variant -- each extra split costs 3 - 5 us of partial-tile traffic through the
-    # device-coherent level -- and its sums are not bit-identical to the tiled kernels'.  DIR_SPLITK=1 enables the shape heuristic
-    # (shapes only, never timing); op.split[B] = S forces a factor.
-    SPLITK = os.environ.get('DIR_SPLITK', '0') == '1'
-
-    def splits(self, B, ho, wo):
-        S = self.split.get(B)
-        if S is None:
-            S = 1
-            tiles = -(-(B * ho * wo) // 128) * -(-self.cout // 128)
-            nk = self.kh * self.kw * self.cin // 64
-            if ConvOp.SPLITK and self.cout % 8 == 0 and tiles <= 128 and nk >= 8:
-                S = max(1, min(16, nk // 4, -(-512 // tiles)))
-            self.split[B] = S
-        return S
-
-    def _splitk_ws(self, d, S, B, dev):
-        key = (B, S, torch.cuda.current_stream(dev).cuda_stream)
-        ws = self._ws.get(key)
-        if ws is None:
-            n = _capi.lib().dir_conv2d_splitk_workspace_bytes(d, S)
-            assert n > 0
-            ws = torch.empty(n, dtype=torch.uint8, device=dev)
-            ws[:16384].zero_()                             # the arrival counters; the kernel leaves them zero
-            self._ws[key] = ws
-        return ws
 
 
 class DualConvOp(object):
@@ -329,16 +261,16 @@ class DualConvOp(object):
     def __call__(self, y, x, out=None, out_coff=0, x_decimated=False):
         """x_decimated: x already holds only the pixels the stride-`stride2` shortcut reads ([B,H,W,Cin2] at y's resolution)"""
         B, H, W, cbuf = y.shape
-        if self.arith is not None and getattr(_TLS, 'calibrating', False):
+        if self.arith is not None and _TLS.calibrating:
             ConvOp._calibrate(self, [y[..., :self.cin], x[..., :self.cin2]])
         if out is None:
             out = torch.empty(B, H, W, self.cout, device=y.device, dtype=self.dtype)
-        if getattr(_TLS, 'capture', None) is not None:
+        if _TLS.capture is not None:
             _TLS.capture.append((self, (y, x), dict(out=out, out_coff=out_coff, x_decimated=x_decimated)))
         d = ConvDesc(B, H, W, self.cin, cbuf, 0, self.cout, out.shape[3], out_coff, 0, 0, 1, 1, 1, 0,
                      DT_F16X3 if self.arith == 'f16x3' else DT_F16X1 if self.arith == 'f16' else _dt(self.dtype), _dt(self.dtype),
                      CONV_RELU if self.relu else 0, 0, 0, self.in_scale)
-        v = _forced_variant() if _forced_variant() is not None else self.variant.get(B, self.variant.get(getattr(_TLS, 'parent_batch', None), 0))
+        v = _variant_for(self, B)
         d.flags |= (v & 0xff) << 8
         d2 = _capi.ConvSrc2(x.shape[1], x.shape[2], self.cin2, x.shape[3], 0, 1 if x_decimated else self.stride2)
         if _capi.PROFILE is not None:
@@ -481,7 +413,7 @@ class BneckChainOp(object):
         pixels of the block output, as [B,H/2,W/2,256] (the last layer1 block when nobody reads c1: dir_bneck_chain_params.out_decimate)"""
         residual, x2 = (None, x) if self.dual is not None else (x, None)
         B, H, W, _ = y1.shape
-        if getattr(_TLS, 'capture_fused', None) is not None:       # tools/energy_profile.py: replayable (allocates its own outputs)
+        if _TLS.capture_fused is not None:       # tools/energy_profile.py: replayable (allocates its own outputs)
             _TLS.capture_fused.append((self, (y1, x), dict(decimate=decimate)))
         self.params.out_decimate = 1 if decimate else 0
         out = torch.empty((B, H // 2, W // 2, 256) if decimate else (B, H, W, 256), device=y1.device, dtype=y1.dtype)
@@ -498,66 +430,20 @@ class BneckChainOp(object):
         return out, y1n
 
 
-def pack_tail_stream(w3, w1n, waves=8, dtype=torch.bfloat16):
-    """dir_bottleneck_tail_forward's weight stream (include/dir_hip.h): conv3.weight [4P, P] and the next conv1.weight [N2, 4P]
-    as bf16 MFMA A-operand fragments in the order the kernel's waves consume them, [4P/512][waves][NBF + NCF][64 lanes][8]
-    (waves = 8: 64-pixel tiles, one workgroup per CU; waves = 4: the thin variant, 32-pixel tiles, two workgroups per CU)."""
-    out_dev = w3.device
-    w3 = w3.detach().float().reshape(w3.shape[0], -1).cpu()        # packed on the host: hundreds of small gathers, once per engine
-    w1n = w1n.detach().float().reshape(w1n.shape[0], -1).cpu()
-    C4, P = w3.shape
-    N2 = w1n.shape[0]
-    assert w1n.shape[1] == C4 and C4 == 4 * P and C4 % 512 == 0 and N2 in (128, 256)
-    dev = w3.device
-    lane = torch.arange(64, device=dev)
-    l32, h, l16, g16 = lane & 31, lane >> 5, lane & 15, lane >> 4
-    e = torch.arange(8, device=dev)
-    KBS = P // 16
-    out = []
-    if waves == 4:
-        ncc = N2 // 128
-        for hf in range(C4 // 512):
-            for w in range(4):
-                for cb in range(4):
-                    for ks in range(KBS):
-                        out.append(w3[(hf * 512 + 128 * w + 32 * cb + l32)[:, None], (16 * ks + 8 * h)[:, None] + e])
-                for ks in range(32):
-                    for cc in range(ncc):
-                        out.append(w1n[((N2 // 4) * w + 32 * cc + l32)[:, None], (hf * 512 + 16 * ks + 8 * h)[:, None] + e])
-        return torch.stack(out).to(dtype).contiguous().to(out_dev)
-    for hf in range(C4 // 512):
-        for w in range(8):
-            for cb in range(2):
-                for ks in range(KBS):
-                    ch = hf * 512 + 64 * w + 32 * cb + l32
-                    k0 = 16 * ks + 8 * h
-                    out.append(w3[ch[:, None], k0[:, None] + e])
-            if N2 == 128:
-                for fc in range(16):
-                    out.append(w1n[(16 * w + l16)[:, None], (hf * 512 + 32 * fc + 8 * g16)[:, None] + e])
-            else:
-                for fc in range(32):
-                    out.append(w1n[(32 * w + l32)[:, None], (hf * 512 + 16 * fc + 8 * h)[:, None] + e])
-    return torch.stack(out).to(dtype).contiguous().to(out_dev)
-
-
 class BneckTailOp(object):
     """dir_bottleneck_tail_forward: conv3 + bn3 + identity + ReLU of a layer2 / layer3 bottleneck and the next block's conv1 + bn1 +
     ReLU in one launch (models/backbone/resnet.py:132-140,122-124): the block output is written once and not read back.  Built from
     the blocks' ConvOps; carries the attributes autotune / export_tuning read from a conv op (single kernel: variant codes are no-ops)."""
     GEOMETRIES = ((128, 128), (128, 256), (256, 256))
-    # the thin variant is built and parity-tested but measured slower at every size (layer3, B = 64: 41.8 vs 34.7 us; it streams the
-    # weights twice as often): off unless DIR_TAIL_THIN_MAX_TILES says otherwise
-    THIN_MAX_TILES = int(os.environ.get('DIR_TAIL_THIN_MAX_TILES', '0'))
-    force_waves = int(os.environ.get('DIR_TAIL_WAVES', '0'))
 
     def __init__(self, c3, c1n):
         self.c3, self.c1n = c3, c1n
         self.cout, self.cin, self.kh, self.kw, self.stride = c3.cout, c3.cin, 1, 1, 1
         self.variant = {}
-        self.stream = {n: pack_tail_stream(c3.w.reshape(c3.cout, c3.cin), c1n.w.reshape(c1n.cout, c1n.cin), n, dtype=c3.dtype) for n in (8, 4)}
-        self.params = {n: _capi.BneckTailParams(_capi.ptr(self.stream[n]), _capi.ptr(c3.scale), _capi.ptr(c3.shift), _capi.ptr(c1n.scale),
-                                                _capi.ptr(c1n.shift), c3.cin, c1n.cout, n, _dt(c3.dtype)) for n in (8, 4)}
+        # the 8-wave stream (64-pixel tiles); the 4-wave "thin" kernel, slower at every size, is reached through functional.bottleneck_tail(waves=4)
+        self.stream = pack_tail_stream(c3.w.reshape(c3.cout, c3.cin), c1n.w.reshape(c1n.cout, c1n.cin), 8, dtype=c3.dtype)
+        self.params = _capi.BneckTailParams(_capi.ptr(self.stream), _capi.ptr(c3.scale), _capi.ptr(c3.shift), _capi.ptr(c1n.scale),
+                                            _capi.ptr(c1n.shift), c3.cin, c1n.cout, 8, _dt(c3.dtype))
 
     @staticmethod
     def applies(c3, c1n, dtype):
@@ -565,26 +451,21 @@ class BneckTailOp(object):
                 and c1n.kh == 1 and c1n.stride == 1 and c1n.cin == c3.cout and c1n.scale is not None and c1n.pre_scale is None
                 and (c3.cin, c1n.cout) in BneckTailOp.GEOMETRIES)
 
-    def __call__(self, y2, x, out=None, y1n=None):
-        """y2: conv2's output [B,H,W,P]; x: the block input [B,H,W,4P] (identity residual) -> (block output, next y1); out / y1n: optional
-        contiguous destinations (the sub-batched high-resolution half writes slices of the whole batch's tensors)"""
+    def __call__(self, y2, x):
+        """y2: conv2's output [B,H,W,P]; x: the block input [B,H,W,4P] (identity residual) -> (block output, next y1)"""
         B, H, W, P = y2.shape
         M = B * H * W
-        if getattr(_TLS, 'capture_fused', None) is not None:
+        if _TLS.capture_fused is not None:
             _TLS.capture_fused.append((self, (y2, x), {}))
-        if out is None:
-            out = torch.empty(B, H, W, self.c3.cout, device=y2.device, dtype=y2.dtype)
-        if y1n is None:
-            y1n = torch.empty(B, H, W, self.c1n.cout, device=y2.device, dtype=y2.dtype)
+        out = torch.empty(B, H, W, self.c3.cout, device=y2.device, dtype=y2.dtype)
+        y1n = torch.empty(B, H, W, self.c1n.cout, device=y2.device, dtype=y2.dtype)
         if _capi.PROFILE is not None:
             c4, n2 = self.c3.cout, self.c1n.cout
             _capi.annotate(family='conv', flops=2.0 * M * (P * c4 + c4 * n2), op=self, dtype='bf16',
                            shape='M=%d tail 1x1(%d->%d)+res+1x1(->%d)' % (M, P, c4, n2),
                            bytes=(M * (P + 2 * c4 + n2) + c4 * P + n2 * c4) * 2)
-        # thin variant (32-pixel tiles, two workgroups per CU) while the fat one would leave workgroups with a single tile
-        waves = self.force_waves or (4 if M // 64 <= self.THIN_MAX_TILES else 8)
-        _capi.check(_capi.lib().dir_bottleneck_tail_forward(C.byref(self.params[waves]), _capi.ptr(y2), _capi.ptr(x), _capi.ptr(out), _capi.ptr(y1n),
-                                                            M, _capi.stream_ptr()), 'dir_bottleneck_tail_forward')
+        _capi.check(_capi.lib().dir_bottleneck_tail_forward(C.byref(self.params), _capi.ptr(y2), _capi.ptr(x), _capi.ptr(out), _capi.ptr(y1n), M,
+                                                            _capi.stream_ptr()), 'dir_bottleneck_tail_forward')
         return out, y1n
 
 
@@ -614,7 +495,6 @@ class BackboneOp(object):
     """ResNet-50 pyramid (models/backbone/resnet.py:243-255): stem as a 4x4 implicit GEMM over 2x2 space-to-depth blocks,
     maxpool, 16 bottlenecks with BN folded into the conv epilogues, the residual add + ReLU fused, and the four projection
     shortcuts folded into their block's conv3 as a second K range (dir_conv2d_dual_forward)."""
-    fold_downsample = os.environ.get('DIR_FOLD_DOWNSAMPLE', '1') != '0'
     fused_stem = os.environ.get('DIR_FUSED_STEM', '1') != '0'       # bf16 mode: conv1 + bn1 + ReLU + maxpool in one launch
     bneck_chain = os.environ.get('DIR_BNECK_CHAIN', '1') != '0'     # bf16 mode, layer1: conv2 + conv3 (+ next conv1) in one launch
     bneck_tail = os.environ.get('DIR_BNECK_TAIL', '1') != '0'       # bf16 mode, layer2 / layer3: conv3 + residual + next conv1 in one launch
@@ -641,15 +521,12 @@ class BackboneOp(object):
                 s3, h3 = bn_fold(sd, q + '.bn3')
                 blk = dict(c1=ConvOp(sd[q + '.conv1.weight'], dt, scale=s1, shift=h1, relu=True),
                            c2=ConvOp(sd[q + '.conv2.weight'], dt, stride=stride, pad=1, scale=s2, shift=h2, relu=True),
-                           c3=ConvOp(sd[q + '.conv3.weight'], dt, scale=s3, shift=h3, relu=True), ds=None)
+                           c3=ConvOp(sd[q + '.conv3.weight'], dt, scale=s3, shift=h3, relu=True))
                 if (q + '.downsample.0.weight') in sd:
                     sd_, hd_ = bn_fold(sd, q + '.downsample.1')
-                    if self.fold_downsample:
-                        blk['dual'] = DualConvOp(sd[q + '.conv3.weight'], s3, h3, sd[q + '.downsample.0.weight'], sd_, hd_, stride, dt)
-                    else:
-                        blk['ds'] = ConvOp(sd[q + '.downsample.0.weight'], dt, stride=stride, scale=sd_, shift=hd_)
+                    blk['dual'] = DualConvOp(sd[q + '.conv3.weight'], s3, h3, sd[q + '.downsample.0.weight'], sd_, hd_, stride, dt)
                 blk['c1'].link_split(blk['c2'])
-                if 'dual' not in blk and blk['ds'] is None:
+                if 'dual' not in blk:
                     blk['c2'].link_split(blk['c3'])
                 blocks.append(blk)
             self.layers.append(blocks)
@@ -661,7 +538,7 @@ class BackboneOp(object):
                 if 'dual' in blk:
                     if BneckChainOp.applies(blk['c2'], None, nxt, dt, dual=blk['dual']):
                         blk['chain'] = BneckChainOp(blk['c2'], None, nxt, dual=blk['dual'])
-                elif blk['ds'] is None and BneckChainOp.applies(blk['c2'], blk['c3'], nxt, dt):
+                elif BneckChainOp.applies(blk['c2'], blk['c3'], nxt, dt):
                     blk['chain'] = BneckChainOp(blk['c2'], blk['c3'], nxt)
 
         # layer2 / layer3 (HBM- / latency-bound 1x1 convs): identity blocks hand their output to the next block's conv1 on chip
@@ -669,7 +546,7 @@ class BackboneOp(object):
             for li in (1, 2):
                 blocks = self.layers[li]
                 for i, blk in enumerate(blocks):
-                    if 'dual' in blk or blk['ds'] is not None or 'chain' in blk:
+                    if 'dual' in blk or 'chain' in blk:
                         continue
                     nxt = blocks[i + 1]['c1'] if i + 1 < len(blocks) else self.layers[li + 1][0]['c1']
                     if BneckTailOp.applies(blk['c3'], nxt, dt):
@@ -683,28 +560,6 @@ class BackboneOp(object):
             u8 = img.dtype == torch.uint8
             _ann('stem', 2.0 * B * 128 * 128 * 64 * 147, img.numel() * img.element_size() + x.numel() * 2 + self.stem_w.numel() * 2,
                  'B=%d 7x7/2 conv + bn + relu + maxpool' % B)
-            nb = self.subbatch
-            last2 = self.layers[1][-1]
-            if nb and nb < B and B % nb == 0 and 'tail' in last2 and not getattr(_TLS, 'capture_fused', None) and not getattr(_TLS, 'no_out_split', False):
-                # Depth-first over sub-batches of `nb` images through the high-resolution half (stem -> layer1 -> layer2): the 64 x 64 and 32 x 32 maps
-                # of one sub-batch (<= 33 MB each at nb = 16) are written and read back while still in the 256 MB Infinity Cache instead of making
-                # HBM round trips of 134 MB per map; layer3 onwards runs on the whole batch.  Same kernels on the same rows: bit-identical.
-                c2 = torch.empty(B, 32, 32, 512, device=dev, dtype=dt)
-                y1n = torch.empty(B, 32, 32, last2['tail'].c1n.cout, device=dev, dtype=dt)
-                _TLS.parent_batch = B
-                try:
-                    for b0 in range(0, B, nb):
-                        isub = img[b0:b0 + nb]
-                        xs = x[b0:b0 + nb]
-                        _ann('stem', 2.0 * nb * 128 * 128 * 64 * 147, isub.numel() * isub.element_size() + xs.numel() * 2 + self.stem_w.numel() * 2,
-                             'B=%d 7x7/2 conv + bn + relu + maxpool' % nb)
-                        _capi.check(L.dir_stem_pool_forward_dt(_capi.ptr(isub), 2 if u8 else 0, _dt(dt), IMAGENET_MEAN, IMAGENET_STD, _capi.ptr(self.stem_w),
-                                                            _capi.ptr(self.stem_scale), _capi.ptr(self.stem_shift), _capi.ptr(xs), nb, 256, 256,
-                                                            _capi.stream_ptr()), 'dir_stem_pool_forward')
-                        self._layers(xs, upto=2, out_last=(c2[b0:b0 + nb], y1n[b0:b0 + nb]))
-                finally:
-                    _TLS.parent_batch = None
-                return [None, c2] + self._layers(c2, start=2, y1=y1n)
             _capi.check(L.dir_stem_pool_forward_dt(_capi.ptr(img), 2 if u8 else 0, _dt(dt), IMAGENET_MEAN, IMAGENET_STD, _capi.ptr(self.stem_w),
                                                 _capi.ptr(self.stem_scale), _capi.ptr(self.stem_shift), _capi.ptr(x), B, 256, 256,
                                                 _capi.stream_ptr()), 'dir_stem_pool_forward')
@@ -726,35 +581,29 @@ class BackboneOp(object):
         return self._layers(x)
 
     decimate_c1 = os.environ.get('DIR_DECIMATE_C1', '1') != '0'     # bf16 mode: c1 is not produced unless asked for (taps / backbone_standalone)
-    subbatch = int(os.environ.get('DIR_SUBBATCH', '0'))             # bf16 mode: images per depth-first pass of stem + layer1 + layer2 (0 = whole batch)
 
-    def _layers(self, x, start=0, upto=4, y1=None, out_last=None):
-        """layers [start, upto) of the pyramid; y1: the first block's conv1 output when the previous layer's last launch already made it;
-        out_last: (block output, next conv1 output) destinations of the LAST block's tail launch (sub-batched half)"""
+    def _layers(self, x):
+        """the four layers of the pyramid on the stem's output -> [c1, c2, c3, c4] (c1 None where it is not produced)"""
         feats = []
+        y1 = None                                                    # the next block's conv1 output, where the previous launch already made it
         x_dec = False                                                # x holds only the even pixels of the previous layer's output (decimate_c1)
-        for li in range(start, upto):
-            blocks = self.layers[li]
+        for li, blocks in enumerate(self.layers):
             for bi, blk in enumerate(blocks):
                 if 'chain' in blk:
                     # the last layer1 block's output is read by layer2's stride-2 projection shortcut only (its conv1 is fused into this launch):
                     # when nobody asks for c1, a quarter of its pixels are written (dir_bneck_chain_params.out_decimate)
                     dec = (self.decimate_c1 and li == 0 and bi == len(blocks) - 1 and blk['chain'].c1n is not None and 'dual' in self.layers[1][0]
-                           and self.layers[1][0]['dual'].stride2 == 2 and 'chain' not in self.layers[1][0] and not getattr(_TLS, 'no_out_split', False))
+                           and self.layers[1][0]['dual'].stride2 == 2 and 'chain' not in self.layers[1][0] and not _TLS.no_out_split)
                     x, y1 = blk['chain'](y1 if y1 is not None else blk['c1'](x), x, decimate=dec)
                     x_dec = dec
                     continue
                 if 'tail' in blk and (x.shape[0] * x.shape[1] * x.shape[2]) % 64 == 0:
-                    if out_last is not None and li == upto - 1 and bi == len(blocks) - 1:
-                        x, y1 = blk['tail'](blk['c2'](y1 if y1 is not None else blk['c1'](x)), x, out=out_last[0], y1n=out_last[1])
-                        continue
                     x, y1 = blk['tail'](blk['c2'](y1 if y1 is not None else blk['c1'](x)), x)
                 elif 'dual' in blk:                                  # conv3 + projection shortcut in one launch
                     x, y1 = blk['dual'](blk['c2'](y1 if y1 is not None else blk['c1'](x)), x, x_decimated=x_dec), None
                     x_dec = False
                 else:
-                    idn = blk['ds'](x) if blk['ds'] is not None else x
-                    x, y1 = blk['c3'](blk['c2'](y1 if y1 is not None else blk['c1'](x)), residual=idn), None
+                    x, y1 = blk['c3'](blk['c2'](y1 if y1 is not None else blk['c1'](x)), residual=x), None
             feats.append(None if x_dec else x)                     # (c1 is not produced when its only reader is the strided shortcut)
         return feats
 
@@ -939,16 +788,15 @@ class ResidualOp(object):
     def __init__(self, sd, p, dtype):
         w = lambda k: sd['%s.%s.conv.weight' % (p, k)]  # noqa: E731
         b = lambda k: sd['%s.%s.conv.bias' % (p, k)]  # noqa: E731
-        self.need_skip = w('skip_layer').shape[0] != w('skip_layer').shape[1]
-        self.skip = ConvOp(w('skip_layer'), dtype, shift=b('skip_layer'))
         s2, h2 = bn_fold(sd, p + '.bn2', b('conv1'))
         self.c1 = ConvOp(w('conv1'), dtype, scale=s2, shift=h2, relu=True, pre=bn_fold(sd, p + '.bn1'), pre_relu=True)
         s3, h3 = bn_fold(sd, p + '.bn3', b('conv2'))
         self.c2 = ConvOp(w('conv2'), dtype, pad=1, scale=s3, shift=h3, relu=True)
         self.c3 = ConvOp(w('conv3'), dtype, shift=b('conv3'))
-        # out = conv3(h) + skip_layer(x): the 1x1 skip projection is a second K range of conv3 (dir_conv2d_dual_forward)
+        # out = conv3(h) + skip_layer(x): the 1x1 skip projection is a second K range of conv3 (dir_conv2d_dual_forward); blocks whose input
+        # and output widths are equal add x itself (hourglass.py:49-52)
         self.dual = None
-        if self.need_skip and self.fold_skip:
+        if w('skip_layer').shape[0] != w('skip_layer').shape[1]:
             one = torch.ones(w('conv3').shape[0], device=w('conv3').device)
             self.dual = DualConvOp(w('conv3'), one, b('conv3'), w('skip_layer'), one, b('skip_layer'), 1, dtype, relu=False)
         self.c1.link_split(self.c2)
@@ -967,7 +815,6 @@ class ResidualOp(object):
                 self.c1.pre_scale, self.c1.pre_shift, self.c1.scale, self.c1.shift, self.c2.scale, self.c2.shift, self.dual.shift)]
                 + [self.c1.cin, self.c1.cout, self.dual.cout, _dt(dtype)]))
 
-    fold_skip = os.environ.get('DIR_FOLD_SKIP', '1') != '0'
     res_chain = os.environ.get('DIR_RES_CHAIN', '1') != '0'        # 16-bit storage, 512 -> 128 -> 256 blocks on 32x32 / 16x16 maps: one launch per block
 
     def _chain_call(self, x, out=None, out_coff=0):
@@ -980,7 +827,7 @@ class ResidualOp(object):
             return None
         if out is None:
             out = torch.empty(B, H, W, self.cout, device=x.device, dtype=x.dtype)
-        if getattr(_TLS, 'capture', None) is not None:       # autotune_energy: this call, replayable
+        if _TLS.capture is not None:       # autotune_energy: this call, replayable
             _TLS.capture.append((self, (x,), dict(out=out, out_coff=out_coff)))
         if _capi.PROFILE is not None:
             m, mid = B * H * W, self.c1.cout
@@ -998,8 +845,7 @@ class ResidualOp(object):
                 return y
         if self.dual is not None:
             return self.dual(self.c2(self.c1(x)), x, out=out, out_coff=out_coff)
-        res = self.skip(x) if self.need_skip else x
-        return self.c3(self.c2(self.c1(x)), out=out, out_coff=out_coff, residual=res)
+        return self.c3(self.c2(self.c1(x)), out=out, out_coff=out_coff, residual=x)
 
 
 class ConvChainOp(object):
@@ -1036,7 +882,7 @@ class ConvChainOp(object):
     def __call__(self, x, out=None):
         c3, c1 = self.c3, self.c1
         B, H, W, cbuf = x.shape
-        if (self.w is None or not self.head_chain or x.dtype != c3.dtype or not x.is_contiguous() or getattr(_TLS, 'calibrating', False)
+        if (self.w is None or not self.head_chain or x.dtype != c3.dtype or not x.is_contiguous() or _TLS.calibrating
                 or (out is not None and (out.dtype != c1.out_dtype or out.shape != (B, H, W, c1.cout) or not out.is_contiguous()))):
             return c1(c3(x), out=out)
         d = self._desc(B, H, W, cbuf)
@@ -1044,7 +890,7 @@ class ConvChainOp(object):
             return c1(c3(x), out=out)
         if out is None:
             out = torch.empty(B, H, W, c1.cout, device=x.device, dtype=c1.out_dtype)
-        if getattr(_TLS, 'capture', None) is not None:       # autotune_energy: this call, replayable
+        if _TLS.capture is not None:       # autotune_energy: this call, replayable
             _TLS.capture.append((self, (x,), dict(out=out)))
         if _capi.PROFILE is not None:
             m = B * H * W
@@ -1135,6 +981,8 @@ class DirEngine(object):
         assert arith in (None, 'f16x3', 'f16') and (arith is None or dtype == torch.float32)     # 'f16': one f16 MFMA per product (DIR_DT_F16X1)
         self.arith = arith
         self.tuned_batches = set()
+        self._tuned_order = {}                 # batch size -> the conv-family layers in first-call order (autotune / import_tuning)
+        self.pending_tuning = None             # {batch size: export_tuning table} handed over by DIR.engine() when the weights were re-packed
         self.sparse_fusion = sparse_fusion     # skip all-zero (tap, bone) K-slabs in the fusion conv (bit-identical)
         _capi.lib()
         self.dtype, self.device = dtype, torch.device(device)
@@ -1277,20 +1125,15 @@ class DirEngine(object):
         factorised = st.bone_fusion is not None and self.factorised_fusion
         if factorised:
             # bf16 throughput mode: bone_proj + fusion conv as a K = 720 reduction, no [B,S,S,2560] bone map.  The per-sample
-            # G tensors need the token features only: they are computed on the side stream, beside the MANO layer.
+            # G tensors need the token features only: they are computed before the MANO layer.
             scratch = torch.empty(L.dir_bone_fusion_scratch_bytes(B), device=dev, dtype=torch.uint8)
-            main, side = torch.cuda.current_stream(), self._side_stream()
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                _ann('bone_fusion', 2.0 * B * 9 * 80 * 64 * 256, 9 * 40 * 64 * 256 * 4 + B * 42 * 64 * 4 + B * 9 * 80 * 256 * (4 if self.dtype == F32 else 2),
-                     'B=%d G = f_end . W (9 taps x 80 bone ends x 256)' % B)
-                _capi.check(L.dir_bone_fusion_prepare(st.bone_fusion, _capi.ptr(emb), _capi.ptr(scratch), B, _capi.stream_ptr()),
-                            'dir_bone_fusion_prepare')
+            _ann('bone_fusion', 2.0 * B * 9 * 80 * 64 * 256, 9 * 40 * 64 * 256 * 4 + B * 42 * 64 * 4 + B * 9 * 80 * 256 * (4 if self.dtype == F32 else 2),
+                 'B=%d G = f_end . W (9 taps x 80 bone ends x 256)' % B)
+            _capi.check(L.dir_bone_fusion_prepare(st.bone_fusion, _capi.ptr(emb), _capi.ptr(scratch), B, sp), 'dir_bone_fusion_prepare')
         res = self.mano_outputs(st.mano, para_l, para_r, off, self._flags[self._stage_index(st)] if self._flags is not None else None)
         vis = torch.empty(B, 1280, S, S, device=dev, dtype=F32) if want_vis else None
         if factorised:
-            main.wait_stream(side)
-            if self.arith is not None and getattr(_TLS, 'calibrating', False):
+            if self.arith is not None and _TLS.calibrating:
                 # split-precision fusion (dir_bone_fusion_params.g_scale): the largest |G| of this batch lands in [2^9, 2^10) of the f16 range
                 amax = float(scratch.view(F32)[:B * 9 * 40 * 256 * 2].abs().max())
                 st.bone_fusion.g_scale = 2.0 ** (10 - math.frexp(amax)[1]) if amax > 0 and math.isfinite(amax) else 1.0
@@ -1330,17 +1173,6 @@ class DirEngine(object):
                                                         _dt(self.dtype), _capi.stream_ptr()), 'dir_upsample2x_bilinear')
 
     factorised_fusion = os.environ.get('DIR_FACTORISED_FUSION', '1') != '0'    # bf16 mode: dir_bone_fusion_forward
-    # Side-stream fork / join inside one forward (skip branches + the fusion's G tensors beside the token path): OFF by default.
-    # It is how the packed-FP32 hazard was found ("Packed FP32 beside another kernel"; fixed at build level), and with
-    # two whole forwards in flight (ForwardPipeline) it no longer pays: 2.44 ms per forward without it against 2.51 ms with it.
-    overlap = os.environ.get('DIR_OVERLAP', '0') == '1'
-
-    def _side_stream(self):
-        if not self.overlap:
-            return torch.cuda.current_stream()
-        if getattr(self, '_side', None) is None:
-            self._side = torch.cuda.Stream(device=self.device)
-        return self._side
 
     # kernel variants a layer can be forced to (include/dir_hip.h: DIR_CONV_VARIANT); 0 = the library's heuristic.  (Code 19, the
     # 64x128 tile on the 3-buffer ring, is not offered: see conv.hip, DIR_RING_64x128.)
@@ -1369,12 +1201,11 @@ class DirEngine(object):
 
     def autotune(self, img, reps=2):
         """Pick the convolution kernel variant per layer for this batch size by timing every candidate inside real
-        forwards (HIP events around each conv launch, side stream off, realistic cache state).  All variants accumulate in
+        forwards (HIP events around each conv launch, one stream, realistic cache state).  All variants accumulate in
         the same order, so the outputs are bit-identical whatever is chosen; a variant that does not apply to a layer falls
         back to the heuristic inside the library.  ~14 x (reps+1) eager forwards, once per (engine, batch size)."""
         B = img.shape[0]
-        saved_overlap, saved_profile = self.overlap, _capi.PROFILE
-        self.overlap = False
+        saved_profile = _capi.PROFILE
         best, covers = {}, {}
         try:
             for v in self.CONV_VARIANTS:
@@ -1394,11 +1225,9 @@ class DirEngine(object):
         finally:
             _TLS.variant = None
             _capi.PROFILE = saved_profile
-            self.overlap = saved_overlap
         for op, (t, v) in best.items():
             op.variant[B] = v
         self.tuned_batches.add(B)
-        self._tuned_order = getattr(self, '_tuned_order', {})
         # first-call order of one forward: stable for a given engine.  One row per LAYER: a chained launch (ConvChainOp) is followed by the layers it
         # covers, whose variant is carried (it is what they run with when the chain is off)
         self._tuned_order[B] = self._layer_ops(dict(op=op, covers=covers.get(op, ())) for op in best)
@@ -1434,14 +1263,13 @@ class DirEngine(object):
         import time as _time
         from . import power
         B = img.shape[0]
-        if B not in getattr(self, '_tuned_order', {}):
+        if B not in self._tuned_order:
             self.autotune(img)                                         # the time-tuned choice first: op order, and the fallback for every op not replayed here
         counter = power.energy_joules() is not None
         if not counter and power.smi_sample() is None:
             raise RuntimeError('autotune_energy: neither the amdsmi energy counter nor rocm-smi gives a reading on this machine')
         if seconds is None:
             seconds = 0.2 if counter else 0.8
-        saved_overlap, self.overlap = self.overlap, False
         torch.cuda.synchronize(self.device)
         if idle_w is None:
             idle_w = power.IDLE_W       # (the reading is a moving average with a time constant near a second: an "idle" sample taken here would still carry load)
@@ -1517,7 +1345,6 @@ class DirEngine(object):
                     c.variant.setdefault(B, 0)                                    # those are measurements); its variant is carried in the table
         finally:
             _TLS.capture, _TLS.variant = None, None
-            self.overlap = saved_overlap
         return {'idle_w': idle_w, 'layers': rows, 'instrument': 'amdsmi energy accumulator, %.2f s windows' % seconds if counter else 'rocm-smi power, last 40 %% of %.2f s windows' % seconds}
 
     TUNING_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'tuning')
@@ -1546,23 +1373,20 @@ class DirEngine(object):
     def import_tuning(self, img, table):
         """apply a table produced by export_tuning on an identically built engine (same layer order, checked by shape)"""
         B = img.shape[0]
-        saved_overlap, saved_profile, self.overlap = self.overlap, _capi.PROFILE, False
+        saved_profile = _capi.PROFILE
         try:
             ops = self._layer_ops(self._profiled_forwards(img, 1))      # (a chained launch stands for every layer it covers)
         finally:
-            _capi.PROFILE, self.overlap = saved_profile, saved_overlap
+            _capi.PROFILE = saved_profile
         if len(ops) != len(table) or any([op.cout, op.cin, op.kh, op.kw, op.stride] != row[:5] for op, row in zip(ops, table)):
             raise ValueError('tuning table does not match this engine')
         for op, row in zip(ops, table):
             op.variant[B] = int(row[5])
         self.tuned_batches.add(B)
-        self._tuned_order = getattr(self, '_tuned_order', {})
         self._tuned_order[B] = ops
 
-    pending_tuning = None          # {batch size: export_tuning table} handed over by DIR.engine() when the weights were re-packed
-
     def export_all_tuning(self):
-        return {B: self.export_tuning(B) for B in getattr(self, '_tuned_order', {})}
+        return {B: self.export_tuning(B) for B in self._tuned_order}
 
     def tune_for(self, img):
         """Make sure batch size img.shape[0] has a kernel choice: a table handed over from the previous engine, else the variants of
@@ -1577,9 +1401,8 @@ class DirEngine(object):
                 return
             except ValueError:
                 pass
-        order = getattr(self, '_tuned_order', {})
-        if order:
-            self.copy_tuning(min(order, key=lambda b: abs(b - B)), B)
+        if self._tuned_order:
+            self.copy_tuning(min(self._tuned_order, key=lambda b: abs(b - B)), B)
         else:
             self.autotune(img)
 
@@ -1641,32 +1464,18 @@ class DirEngine(object):
         c1, c2, c3, c4 = feats
         cat4 = torch.empty(B, 16, 16, 2304, device=dev, dtype=dt)
         cat3 = torch.empty(B, 32, 32, 512, device=dev, dtype=dt)
-        # The two skip branches depend on the backbone only.  With `overlap` (off by default, see the class attribute) they run on
-        # a side stream: skip_layer4 beside init_head / MANO, skip_layer3 beside stage 1's token path.  Otherwise `side` is the
-        # current stream and the waits below are no-ops.
-        main = torch.cuda.current_stream()
-        side = self._side_stream()
-        ev_tok = torch.cuda.Event()
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            self.res['skip_layer4'](c3, out=cat4, out_coff=2048)
-            ev_s4 = torch.cuda.Event()
-            ev_s4.record()
+        # everything on the current stream, in one fixed order; the two skip branches depend on the backbone only and come first in their stage
+        self.res['skip_layer4'](c3, out=cat4, out_coff=2048)
         init = self.init_regressor(c4)
         # ---- stage 1 @16x16 (models/dir.py:442-456)
         self.upsample_into(c4, cat4, 0)
-        main.wait_event(ev_s4)
         enh4_in = torch.empty(B, 16, 16, 512, device=dev, dtype=dt)             # cat(fusion_feat, img_feat)
         self.res['fusion_layer4'](cat4, out=enh4_in, out_coff=0)
-        ev_tok.record()
-        with torch.cuda.stream(side):
-            side.wait_event(ev_tok)
-            self.res['skip_layer3'](c2, out=cat3, out_coff=256)
+        self.res['skip_layer3'](c2, out=cat3, out_coff=256)
         r4 = self.stage(self.stage4, enh4_in, 512, init, enh4_in, 256, False)
         e4 = self.res['enhance_layer4'](enh4_in)
         # ---- stage 2 @32x32 (models/dir.py:459-471)
         self.upsample_into(e4, cat3, 0)
-        main.wait_stream(side)
         enh3_in = torch.empty(B, 32, 32, 512, device=dev, dtype=dt)
         self.res['fusion_layer3'](cat3, out=enh3_in, out_coff=0)
         nx = len(self.stages_x)

@@ -4,6 +4,7 @@ import torch
 
 from . import _capi
 from ._capi import CONV_PRE_RELU, CONV_RELU, DT_BF16, DT_F16, DT_F16X1, DT_F16X1P, DT_F16X3, DT_F16X3P, DT_F32, ConvDesc
+from .packing import pack_stream_weights, pack_tail_stream
 
 
 def _dt(t):
@@ -243,7 +244,6 @@ def bottleneck_tail(y2, w3, s3, h3, residual, w1n, s1n, h1n, waves=8):
     """models/backbone/resnet.py:132-140 (+ :122-124 of the next block) in one launch, layer2 / layer3 geometry, bf16 NHWC.
     y2 [B,H,W,P]; w3 [4P,P]; residual [B,H,W,4P] (the block input); w1n [N2,4P]  ->  (out [B,H,W,4P], y1_next [B,H,W,N2])"""
     import ctypes as C
-    from .engine import pack_tail_stream
     _capi.require_cuda(y2, residual)
     B, H, W, P = y2.shape
     C4, N2 = w3.shape[0], w1n.shape[0]
@@ -261,7 +261,6 @@ def conv1x1_stream(x, w_nk, scale=None, shift=None, relu=False, pre_scale=None, 
                    out=None, out_coff=0, in_coff=0, cin=None, variant=0):
     """dir_conv1x1_stream_forward: y = act(scale * (x[..., in_coff:in_coff+cin] . W1^T + x2[::stride2, ::stride2] . W2^T) + shift), bf16 NHWC.
     w_nk: fp32/bf16 [Cout, cin (+ Cin2)] (second source's columns appended); variant 22: 64-pixel workgroups (same bits)"""
-    from .engine import pack_stream_weights
     _capi.require_cuda(x, x2, out)
     B, H, W, cbuf = x.shape
     Cout, K = w_nk.shape

@@ -520,7 +520,8 @@ int dir_train_pack_conv_weights(const dir_train_weight* table, const int* wg_sta
  * (scale / shift, residual, ReLU).  The summation order differs from the unsplit kernels': outputs agree to bf16 rounding, not bit for
  * bit.  workspace: dir_conv2d_splitk_workspace_bytes(d, splits) bytes, 16-byte aligned, its first 16 KiB ZERO before the first use (the
  * kernel leaves them zero); one workspace must not be shared by launches that can run concurrently.  splits == 1 = dir_conv2d_forward.
- * EXPERIMENTAL, off by default (DIR_SPLITK=1 / ConvOp.split): the cross-workgroup hand-over publishes the partial tiles as relaxed
+ * EXPERIMENTAL, not selected by the engine (functional.conv2d_nhwc(splits=...) calls it): the cross-workgroup hand-over publishes the
+ * partial tiles as relaxed
  * agent-scope atomic stores that are drained (s_waitcnt vmcnt(0)) before a relaxed ticket increment -- sufficient on gfx950, where a
  * completed sc1 store is visible device-wide, but NOT a release / acquire pair in the HIP memory model (a formal release on the ticket
  * costs an L2 write-back per workgroup: +12 us per split, which erases the gain).  Measured no faster than the tiled kernels at the

@@ -354,7 +354,7 @@ def test_full_size_batch_64_rows_equal_the_golden_pinned_small_batch(golden, dir
     eng.autotune(batches[0])                                     # the bench's per-layer kernel choice for this batch size
     pipe = ForwardPipeline(eng, batches)
     # soak: both slots relaunched back to back for several rounds (each overlapping the other) before the checked round -- every
-    # round must reproduce the one-at-a-time result bit for bit (this is what caught the side-stream fork / join, engine.overlap)
+    # round must reproduce the one-at-a-time result bit for bit (this is what caught the side-stream fork / join the engine once had)
     src = [b.clone() for b in batches]
     ref = []
     for b in batches:

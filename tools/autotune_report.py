@@ -11,7 +11,6 @@ eng = E.DirEngine(sd, dtype=torch.float16 if os.environ.get('DT', 'f16') == 'f16
 B = int(os.environ.get('B', 64))
 img = torch.randn(B, 3, 256, 256, device='cuda')
 eng.forward(img); torch.cuda.synchronize()
-eng.overlap = False
 times, info, order = {}, {}, []
 for v in eng.CONV_VARIANTS:
     E._TLS.variant = v

@@ -18,7 +18,6 @@ sd = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in synth.synth_state
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 big = torch.randn(B, 3, 256, 256, device='cuda')
 eng = E.DirEngine(sd, dtype=torch.bfloat16)
-eng.overlap = False
 seen = {}
 
 
@@ -26,7 +25,7 @@ def wrap(cls):
     orig = cls.__call__
 
     def call(self, *a, **kw):
-        if self.w_stream is None or E._forced_variant() is not None:
+        if self.w_stream is None or E._TLS.variant is not None:
             return orig(self, *a, **kw)
         out = orig(self, *a, **kw)
         ref = out.clone()

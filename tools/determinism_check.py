@@ -22,8 +22,7 @@ def same(a, b):
 
 
 eng = E.DirEngine(sd, dtype=torch.bfloat16)
-if os.environ.get('NO_OVERLAP'): eng.overlap = False
-print('overlap', eng.overlap, 'factorised', eng.factorised_fusion)
+print('factorised', eng.factorised_fusion)
 base = [snap(eng.forward(im)) for im in imgs]
 torch.cuda.synchronize()
 for trial in range(int(os.environ.get('TRIALS', '2'))):

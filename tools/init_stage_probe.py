@@ -19,6 +19,15 @@ def mpjpe(o):
     return out
 
 
+def layers_from(bb, x, start):
+    """layers start+1 .. 4 of a (fp32: unfused) backbone on the map x"""
+    saved, bb.layers = bb.layers, bb.layers[start:]
+    try:
+        return bb._layers(x)
+    finally:
+        bb.layers = saved
+
+
 e16 = E.DirEngine(sd, dtype=torch.bfloat16)
 e16.bb.decimate_c1 = False
 e32 = E.DirEngine(sd, dtype=torch.float32)
@@ -31,8 +40,8 @@ print('  all f16 arithmetic (fp32 maps)   ', mpjpe(ef.forward(img)[0]))
 for upto in (3, 2, 1):
     feats = e16.bb(img)                                   # bf16 c1..c4
     x = feats[upto - 1].float().contiguous()             # the bf16 map handed to fp32 layers upto+1 .. 4
-    c = e32.bb._layers(x, start=upto)                    # fp32 layers
+    c = layers_from(e32.bb, x, upto)                     # fp32 layers
     init = e32.init_regressor(c[-1])
     print('  bf16 up to c%d, fp32 from layer%d on ' % (upto, upto + 1), mpjpe(init))
-    init = ef.init_regressor(ef.bb._layers(x, start=upto)[-1])
+    init = ef.init_regressor(layers_from(ef.bb, x, upto)[-1])
     print('  bf16 up to c%d, f16 arithmetic after ' % upto, mpjpe(init))

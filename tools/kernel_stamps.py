@@ -9,7 +9,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 shapes = {k: tuple(v) for k, v in json.load(open(os.path.join(ROOT, 'tests', 'golden', 'manifest_dir.json'))).items()}
 sd = {k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in synth.synth_state_dict(shapes, 1234).items()}
 eng = E.DirEngine(sd, dtype=torch.bfloat16)
-eng.overlap = False
 img = torch.randn(64, 3, 256, 256, device='cuda')
 for _ in range(3):
     eng.forward(img)
