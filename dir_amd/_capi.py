@@ -149,6 +149,19 @@ class OneEuroSegment(C.Structure):       # dir_one_euro_segment
     _fields_ = [('n_points', C.c_int32), ('dims', C.c_int32), ('speed_scale', C.c_float)]
 
 
+class ManoParaSmoothHand(C.Structure):  # dir_mano_para_smooth_hand
+    _fields_ = [(n, C.c_void_p) for n in ('para', 'cam_px', 'raw_verts', 'raw_joints', 'raw_joints_px', 'smoothed', 'verts', 'joints', 'joints_px',
+                                          'updated', 'state')]
+
+
+class ManoParaSmoothOpts(C.Structure):  # dir_mano_para_smooth_opts
+    _fields_ = [(n, C.c_double) for n in ('fps', 'min_cutoff', 'beta', 'd_cutoff', 'rot_speed_scale', 'cam_speed_scale')] + [
+        ('max_gap', C.c_int32), ('shape_frames', C.c_int32)]
+
+
+MANO_PARA_SMOOTH_FIELDS = ('measures', 'y1', 'y2', 'x1', 'x2', 'prev', 'vel', 'n_shape', 'age', 'run', 'count')     # DIR_MANO_PARA_SMOOTH_FIELDS = 11
+
+
 class GuardState(C.Structure):           # dir_guard_state
     _fields_ = [('sumsq', C.c_double), ('norm', C.c_double), ('bc1', C.c_double), ('applied', C.c_longlong), ('skipped', C.c_longlong),
                 ('skipped_in_row', C.c_longlong), ('clipped', C.c_longlong), ('coef', C.c_float), ('bc2_sqrt', C.c_float),
@@ -160,7 +173,7 @@ class RenderLights(C.Structure):         # dir_render_lights
                 ('shininess', C.c_float)]
 
 
-ABI_VERSION = 52         # DIR_ABI_VERSION (include/dir_hip.h)
+ABI_VERSION = 53         # DIR_ABI_VERSION (include/dir_hip.h)
 DT_F32, DT_BF16, DT_F16X3, DT_F16X1, DT_F16X3P, DT_F16X1P, DT_F16 = 0, 1, 3, 4, 5, 6, 7      # DT_F16: f16 STORAGE (round 5)
 CONV_RELU, CONV_PRE_RELU = 1, 2
 
@@ -315,6 +328,8 @@ _SIGNATURES = {
     'dir_crop_frames_area': (C.c_int, [_p, C.c_longlong, _p, _p, _p, _i, _i, _p, _p, _p, _p]),
     'dir_one_euro_state_bytes': (C.c_longlong, [_i, _i, C.POINTER(C.c_longlong)]),
     'dir_one_euro_step': (C.c_int, [_p, _p, _i, C.POINTER(OneEuroSegment), _i, C.c_double, C.c_double, C.c_double, C.c_double, _i, _p, _p, _p, _p]),
+    'dir_mano_para_smooth_state_bytes': (C.c_longlong, [C.POINTER(C.c_longlong)]),
+    'dir_mano_para_smooth_step': (C.c_int, [C.POINTER(ManoTables), C.POINTER(ManoParaSmoothHand), _p, C.POINTER(ManoParaSmoothOpts), _i, _i, _p]),
 }
 
 
@@ -327,7 +342,7 @@ _pending = {}
 _NO_PROFILE = ('dir_conv2d_as_supported', 'dir_conv2d_as_chain_supported', 'dir_residual_chain_supported', 'dir_abi_version', 'dir_last_error', 'dir_device_info', 'dir_launch_log_reset', 'dir_launch_log_get', 'dir_launch_log_note',
                'dir_bone_fusion_scratch_bytes', 'dir_dense_losses_workspace_bytes', 'dir_dense_losses_backward_workspace_bytes',
                'dir_gemm_f32_splitk_workspace_bytes', 'dir_bn_train_workspace_bytes', 'dir_bn_sync_workspace_bytes', 'dir_bn_frozen_workspace_bytes', 'dir_jpeg_planes_bytes', 'dir_render_workspace_bytes', 'dir_render_adjacency_bytes', 'dir_render_shaded_workspace_bytes', 'dir_colsum_workspace_bytes', 'dir_conv2d_wgrad_workspace_bytes', 'dir_conv2d_wgrad_f16x3_workspace_bytes',
-               'dir_one_euro_state_bytes', 'dir_grad_norm_workspace_bytes')
+               'dir_one_euro_state_bytes', 'dir_mano_para_smooth_state_bytes', 'dir_grad_norm_workspace_bytes')
 
 
 def annotate(**kw):

@@ -3,7 +3,7 @@ the GPU) -> DirEngine.forward -> predictions in FRAME pixels.
 
     python -m dir_amd.apps.predict --model CKPT --input DIR|FILES --out DIR [--boxes boxes.json] [--track] [--ratio 0.8] [--bs 32]
                                    [--stage 2] [--dtype f16|bf16|f32] [--workers 8] [--pictures] [--joints] [--obj] [--antialias]
-                                   [--smooth] [--smooth_box] [--fps 30] [--min_cutoff 1.0] [--beta 0.007] [--d_cutoff 1.0]
+                                   [--smooth] [--smooth_space point|para] [--shape_frames N] [--smooth_box] [--fps 30] [--min_cutoff 1.0] [--beta 0.007] [--d_cutoff 1.0]
                                    [--keypoints FILE] [--refine_iters 50] [--refine_lr 0.01] [--refine_prior 1e-3]
 
 Input: image files (jpg / jpeg / png / bmp) in natural name order, decoded to BGR on the host with Pillow by worker threads that never
@@ -30,6 +30,14 @@ usable frame with dt = frames since the last one / --fps; after more than round(
 --beta, --d_cutoff are the filter's parameters; the defaults are the paper's (Casiez et al. 2012) and are NOT tuned on real video.  At the
 end <out>/jitter.json (<out>/<sequence>/jitter.json with sub-directories) holds, per stream, the mean second difference per point per frame
 of the raw and of the filtered values, and a line before the last one prints their means in mm/frame^2 and px/frame^2.
+--smooth_space para (with --track --smooth; default point): the filter runs in MANO PARAMETER space instead (utils/smooth.py
+ParameterSmoother, csrc/para_smooth.hip, the rule in include/dir_hip.h): the root rotation on SO(3), the 15 finger joints per joint in
+axis-angle, the frame camera as three scalars, and ONE shape per sequence -- the betas are averaged over the first --shape_frames usable frames
+(default round(--fps)) and then frozen.  left / right hold the mesh, joints and 2-D joints REGENERATED from the filtered parameters by the MANO
+forward in the same launch (so the 2-D joints are the projection of the 3-D joints, which are the joints of the mesh, and bone lengths hold once
+the shape is frozen); "mano" holds the parameters themselves and "shape_frozen" whether each hand's shape is fixed yet; jitter.json gains the
+bone flicker (mean change of a bone's length from frame to frame, mm).  rot_speed_scale (100, a guess of 100 mm per radian) and the other
+defaults are NOT tuned.  Without this flag every byte written is what it was.
 --smooth_box (with --track, separate from --smooth, off by default): the next tracked box (its centre and half side) goes through a filter
 of its own before the next crop is made, on the device; a first box and a held box are unchanged.  This changes the crops, and with them
 every prediction after frame 1.  These flags without --track are an error.
@@ -55,6 +63,8 @@ Output per image, <out>/<stem>.json (in --track with sub-directories <out>/<sequ
   offset                 the predicted offset between the hands' roots (pd_offset)
   antialiased            only with --antialias: true where the crop was made with the anti-aliased rule (it shrinks the frame)
   smoothed, raw          only with --smooth: true, and {"left", "right", "offset"} as they are without the flag
+  mano, shape_frozen     only with --smooth_space para: {"left": {"root_6d" [6], "pose_aa" [45] axis-angles with the mean included, "betas" [10],
+                         "camera_px" [3]}, "right": ...} -- the filtered hand model behind left / right -- and [bool, bool]
   box_smoothed           only with --smooth_box: true where this frame's matrix went through the box filter
   refined, refined_hands, unrefined   only with --keypoints: true, {"left": bool, "right": bool} (which hands the fit replaced), and
                          {"left", "right"} as they are without the flag
@@ -159,7 +169,8 @@ class Tracker(object):
     crop_frames(antialias=True) and `area` int32 [B] says which of them got the anti-aliased rule (None otherwise).
 
     smooth (True, or a dict of utils.smooth.OneEuro's parameters; needs track): after every forward the stage goes through a
-    PredictionSmoother sized by the first step; `smoothed` is its result (frame space) and drawn(outs) the stage dict to draw.  smooth_box
+    PredictionSmoother sized by the first step -- with 'space': 'para' in the dict (and optionally 'shape_frames', 'rot_speed_scale',
+    'cam_speed_scale') through a ParameterSmoother on the stage's own MANO tables, the forward then run with want_para; `smoothed` is its result (frame space) and drawn(outs) the stage dict to draw.  smooth_box
     (likewise): the next matrices go through smooth_matrices before the next crop; `box_smoothed` int32 [B] says which of the current
     matrices did.  Neither reads anything back.
 
@@ -177,6 +188,11 @@ class Tracker(object):
         if (self.smooth is not None or self.smooth_box is not None) and not self.track:
             raise ValueError('Tracker: smooth and smooth_box need track=True')
         self.smoother = self.box_filter = self.smoothed = self.box_smoothed = self._box_updated = None
+        self.smooth_space = 'point' if self.smooth is None else self.smooth.pop('space', 'point')
+        if self.smooth_space not in ('point', 'para'):
+            raise ValueError("Tracker: smooth['space'] is 'point' or 'para', got %r" % (self.smooth_space,))
+        if self.smooth_space == 'point' and 'shape_frames' in (self.smooth or {}):
+            raise ValueError("Tracker: shape_frames needs smooth['space'] = 'para'")
         self.refine = None if refine is None else dict(refine)
         self.unrefined = self.refined_hands = None
 
@@ -244,7 +260,9 @@ class Tracker(object):
         else:
             crops, status = CR.crop_frames(batch, self.M, self.valid, self.size, return_status=True)
         self.valid = self.valid * (status == 0).to(torch.int32)            # a crop the kernel refused is black: the image is not valid
-        if self.refine is None:
+        if self.refine is None and self.smooth_space == 'para':
+            outs = self.eng.forward(crops, want_proj_feat=False, want_para=True)
+        elif self.refine is None:
             outs = self.eng.forward(crops, want_proj_feat=False)
         else:
             outs = list(self.eng.forward(crops, want_proj_feat=False, want_para=True))
@@ -260,7 +278,9 @@ class Tracker(object):
             self._next = (M_next, ok, self.valid)
         if self.smooth is not None:
             from ..utils import smooth as SM
-            if self.smoother is None:
+            if self.smoother is None and self.smooth_space == 'para':
+                self.smoother = SM.ParameterSmoother(list(self._stage_tables()), B, self.size, device=dev, **self.smooth)
+            elif self.smoother is None:
                 self.smoother = SM.PredictionSmoother(B, self.size, device=dev, **self.smooth)
             self.smoothed = self.smoother.step(outs[self.stage], self.M, self.valid)
         return crops, outs
@@ -296,6 +316,10 @@ def _records(paths, batch, boxes_used, tr, outs, stage, keep_stage):
         t['s_offset'] = fr['offset']
         for s in SIDES:
             t['s_px_' + s], t['s_xyz_' + s], t['s_cam_' + s] = fr['joints_px_' + s], fr['joint_xyz_' + s], fr['camera_px_' + s]
+            if tr.smooth_space == 'para':
+                t['s_mano_' + s] = fr['smoothed_' + s]
+        if tr.smooth_space == 'para':
+            t['s_shape_count'] = fr['shape_count']
         if keep_stage:
             t.update(('s_' + k, v) for k, v in tr.smoother.crop_stage().items())
     if tr.box_smoothed is not None:
@@ -326,6 +350,11 @@ def _records(paths, batch, boxes_used, tr, outs, stage, keep_stage):
                         'camera_px': {'scale': num(float(h['s_cam_' + s][j][0])), 'trans': num(h['s_cam_' + s][j][1:3].tolist())}}
             r['offset'] = num(h['s_offset'][j].reshape(-1).tolist())
             r['smoothed'] = True
+            if 's_shape_count' in h:                                          # smooth_space para: the hand model behind left / right
+                r['mano'] = {s: {'root_6d': num(h['s_mano_' + s][j][0:6].tolist()), 'pose_aa': num(h['s_mano_' + s][j][6:51].tolist()),
+                                 'betas': num(h['s_mano_' + s][j][51:61].tolist()), 'camera_px': num(h['s_mano_' + s][j][61:64].tolist())} for s in SIDES}
+                n = tr.smoother.shape_frames
+                r['shape_frozen'] = [bool(n > 0 and c >= n) for c in h['s_shape_count'][j].tolist()]
         if 'box_smoothed' in h:
             r['box_smoothed'] = bool(h['box_smoothed'][j])
         if 'area' in h:
@@ -386,8 +415,15 @@ def sequence_jitter(tr, steps):
 
     def num(a):
         return [v if np.isfinite(v) else None for v in a.tolist()]
-    return {i: {'streams': j['streams'], 'points': [p for _, p, _, _ in SM.STREAMS], 'frames': int(j['frames'][row]), 'raw': num(j['raw'][row]),
-                'filtered': num(j['filtered'][row]), 'sums': j['sums'][row].tolist()} for row, (i, _) in enumerate(steps[0])}
+    out = {i: {'streams': j['streams'], 'points': [p for _, p, _, _ in SM.STREAMS], 'frames': int(j['frames'][row]), 'raw': num(j['raw'][row]),
+               'filtered': num(j['filtered'][row]), 'sums': j['sums'][row].tolist()} for row, (i, _) in enumerate(steps[0])}
+    if 'bone_flicker' in j:                        # smooth_space para: a hand counts its own frames; bone flicker in mm per bone per frame
+        f = j['bone_flicker']
+        for row, (i, _) in enumerate(steps[0]):
+            out[i].update(space='para', stream_frames=j['stream_frames'][row].tolist(),
+                          bone_flicker={'hands': list(SIDES), 'bones': 20, 'frames': f['frames'][row].tolist(), 'raw_mm': num(f['raw'][row] * 1000.0),
+                                        'filtered_mm': num(f['filtered'][row] * 1000.0), 'sums': f['sums'][row].tolist()})
+    return out
 
 
 def jitter_summary(jitters):
@@ -395,13 +431,25 @@ def jitter_summary(jitters):
     means per point per frame over all sequences; NaN when no frame was counted"""
     mm, px = np.zeros(3), np.zeros(3)
     for j in jitters:
-        for name, p, (raw, fil) in zip(j['streams'], j['points'], j['sums']):
+        frames = j.get('stream_frames', [j['frames']] * len(j['streams']))
+        for name, p, (raw, fil), n in zip(j['streams'], j['points'], j['sums'], frames):
             if name.startswith('camera_px'):
                 continue
             acc = px if name.startswith('joints_px') else mm
-            acc += (raw, fil, p * j['frames'])
+            acc += (raw, fil, p * n)
     with np.errstate(invalid='ignore', divide='ignore'):
         return tuple(mm[:2] / mm[2] * 1000.0), tuple(px[:2] / px[2])
+
+
+def flicker_summary(jitters):
+    """[sequence_jitter records of a smooth_space para walk] -> (raw, filtered) bone flicker in mm per bone per frame over all sequences and hands"""
+    acc = np.zeros(3)
+    for j in jitters:
+        f = j['bone_flicker']
+        for (raw, fil), n in zip(f['sums'], f['frames']):
+            acc += (raw, fil, f['bones'] * n)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return tuple(acc[:2] / acc[2] * 1000.0)
 
 
 def predict(eng, frames, boxes=None, ratio=0.8, stage=2, bs=32, track=False, keep_stage=False, keep_crops=False, antialias=False, smooth=None,
@@ -417,6 +465,8 @@ def predict(eng, frames, boxes=None, ratio=0.8, stage=2, bs=32, track=False, kee
     shrinks its frame; every record then has 'antialiased'.
     smooth / smooth_box (with `track`; True or a dict of utils.smooth.OneEuro's parameters): Tracker's.  With smooth a record's left, right
     and offset are filtered, 'raw' holds the unfiltered ones, and keep_stage adds 'stage_smoothed' (PredictionSmoother.crop_stage);
+    smooth={'space': 'para', ...} smooths in MANO parameter space instead (utils.smooth.ParameterSmoother: records gain 'mano' and 'shape_frozen', the
+    jitter records 'bone_flicker');
     return_jitter -> (records, [sequence_jitter per sequence]).
     keypoints: one {"left": [[x, y, conf] x 21], "right": ...} or None per image (with `track` one such list per sequence), frame pixels: the
     stage is refined against them (the module docstring's --keypoints; refine_iters, refine_lr, refine_prior); every record then has
@@ -551,6 +601,11 @@ def main(argv=None):
     ap.add_argument('--obj', action='store_true', help='write <stem>.obj: both predicted hands in one frame')
     ap.add_argument('--antialias', action='store_true', help='anti-aliased crops where the crop shrinks the frame (hand boxes larger than 256 px)')
     ap.add_argument('--smooth', action='store_true', help='with --track: One-Euro temporal smoothing of every prediction stream, in frame space; writes jitter.json')
+    ap.add_argument('--smooth_space', choices=['point', 'para'], default='point',
+                    help='with --track --smooth: filter every output point on its own (point), or the MANO parameters -- root rotation on SO(3), finger joints in '
+                         'axis-angle, one shape per sequence -- and regenerate mesh and joints from them (para)')
+    ap.add_argument('--shape_frames', type=int, default=None, help='with --smooth_space para: the usable frames the shape is averaged over before it is frozen '
+                                                                   '(default round(fps); 0: the betas pass through)')
     ap.add_argument('--smooth_box', action='store_true', help='with --track: smooth the next tracked box before the next crop is made (changes the crops)')
     ap.add_argument('--fps', type=float, default=None, help='the frame rate of the sequence (default 30)')
     ap.add_argument('--min_cutoff', type=float, default=None, help='One-Euro: the cutoff at rest, Hz (default 1.0, the paper\'s; not tuned on real video)')
@@ -570,6 +625,10 @@ def main(argv=None):
         ap.error('--fps, --min_cutoff, --beta and --d_cutoff need --smooth or --smooth_box')
     if any(v <= 0 for k, v in params.items() if k != 'beta') or params.get('beta', 0.0) < 0:
         ap.error('--fps, --min_cutoff and --d_cutoff must be positive and --beta not negative')
+    if (opt.smooth_space != 'point' or opt.shape_frames is not None) and not (opt.track and opt.smooth):
+        ap.error('--smooth_space and --shape_frames need --track --smooth')
+    if opt.shape_frames is not None and (opt.smooth_space != 'para' or opt.shape_frames < 0):
+        ap.error('--shape_frames needs --smooth_space para and must not be negative')
     rp = {k: getattr(opt, 'refine_' + k) for k in ('iters', 'lr', 'prior') if getattr(opt, 'refine_' + k) is not None}
     if rp and not opt.keypoints:
         ap.error('--refine_iters, --refine_lr and --refine_prior need --keypoints')
@@ -598,12 +657,17 @@ def main(argv=None):
             renderer = V.mano_two_hands_shaded_renderer(right_faces=mano['right'].get_faces(), dense_color=np.zeros((V.NV_HAND, 3)), img_size=SIZE,
                                                         device=eng.device)
     jitters = []
+    smooth_arg = (params or True) if opt.smooth else None
+    if opt.smooth and opt.smooth_space == 'para':
+        smooth_arg = dict(params, space='para', **({} if opt.shape_frames is None else {'shape_frames': opt.shape_frames}))
     n, sec, wait = run(eng, sequences, opt.out, boxes, opt.ratio, opt.stage, opt.bs, opt.track, opt.workers, opt.pictures, opt.joints, opt.obj,
-                       renderer, faces, opt.antialias, (params or True) if opt.smooth else None, (params or True) if opt.smooth_box else None, jitters, keypoints, rp)
+                       renderer, faces, opt.antialias, smooth_arg, (params or True) if opt.smooth_box else None, jitters, keypoints, rp)
     print('waited %.2f s of them for decoded frames' % wait)
     if opt.smooth:
         mm, px = jitter_summary(jitters)
         print('jitter, raw -> smoothed: %.4g -> %.4g mm/frame^2 (meshes, 3-D joints, offset), %.4g -> %.4g px/frame^2 (2-D joints)' % (mm + px))
+        if opt.smooth_space == 'para':
+            print('bone flicker, raw -> smoothed: %.4g -> %.4g mm/frame per bone' % flicker_summary(jitters))
     print('%d images in %.1f s: %.0f images/s' % (n, sec, n / max(sec, 1e-9)))
     return n
 

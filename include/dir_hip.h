@@ -29,7 +29,7 @@ extern "C" {
 #define DIR_E_LAUNCH (-2)   /* hipLaunchKernel / HIP runtime error          */
 #define DIR_E_NODEVICE (-3) /* no gfx950 device visible                     */
 
-#define DIR_ABI_VERSION 52
+#define DIR_ABI_VERSION 53
 
 int dir_abi_version(void);
 const char* dir_last_error(void);
@@ -1418,6 +1418,98 @@ typedef struct dir_one_euro_segment {
 long long dir_one_euro_state_bytes(int F, int S, long long* offsets);
 int dir_one_euro_step(const float* x, const int32_t* valid, int B, const dir_one_euro_segment* segments, int S, double fps, double min_cutoff,
                       double beta, double d_cutoff, int max_gap, void* state, float* y, int32_t* updated, void* stream);
+
+/* ---- smoothing in MANO parameter space (ABI 53; csrc/para_smooth.hip; nothing in the reference) ----
+ * dir_one_euro_step filters every output point alone: bone lengths are not kept, the streams do not agree with one another and no parameters
+ * come out.  dir_mano_para_smooth_step filters where a hand is a hand -- the root rotation on SO(3), the 15 finger joints per joint in
+ * axis-angle, the frame camera as three scalars, ONE shape per sequence -- and regenerates the mesh, the joints and the 2-D joints from the
+ * filtered parameters with the MANO forward, in the same launch.  The rule is restated in torch (float64 and float32) by
+ * tests/helpers/para_smooth_ref.py.  One call is one frame of B sequences x `hands` (1 or 2); one 256-lane workgroup per (sequence, hand); the
+ * state is updated in place; no atomics, no workspace, no host read; capturable in a graph.
+ *
+ * Per hand (dir_mano_para_smooth_hand; every pointer a device pointer):
+ *   para           [B,64]  the layout of pd_mano_para_*: 6D root | 45 PCA coefficients | 10 betas | 3 crop-camera values.  Components 61:64 are
+ *                          NOT read: the crop moves between frames, the frame does not, so the camera comes in as
+ *   cam_px         [B,3]   frame_camera's (scale_px, trans_px x, trans_px y)
+ *   raw_verts [B,778,3], raw_joints [B,21,3], raw_joints_px [B,21,2]   optional (NULL): the unfiltered streams, for the raw side of the measures only
+ *   smoothed       [B,64]  six | a_y [45] | b_y [10] | c_y [3].  This is NOT a pd_mano_para: 6:51 are the 45 AXIS-ANGLE components with hands_mean
+ *                          included (not PCA coefficients), and 61:64 are FRAME pixels (not the crop camera).  six and b_y may be fed to
+ *                          dir_mano_forward as they are: six reproduces the R_y the kernel used bit for bit.
+ *   verts [B,778,3], joints [B,21,3], joints_px [B,21,2]   the forward at the filtered parameters;  updated int32 [B]: 0, 1 or 2 as below
+ *   state          B rows of dir_mano_para_smooth_state_bytes(offsets) bytes, 16-byte aligned, zeroed by the caller before the first frame; rows
+ *                  are per (sequence, hand), and the first B rows of a larger state are the state of a smaller batch (sequences end from the tail)
+ * valid int32 [B] or NULL is shared by the hands.  tables_host / hands_host: HOST arrays of `hands` entries, passed to the kernel by value.
+ *
+ * State row: offsets[DIR_MANO_PARA_SMOOTH_FIELDS] (or NULL) receives the byte offsets of
+ *   measures  double [8]: raw, filtered sums of mesh_xyz | joint_xyz | joints_px jitter | bone flicker
+ *   y1, y2    float32 [2440] each: the last two outputs, verts [2334] | joints [63] | joints_px [42] | pad;   x1, x2: the same of the raw streams
+ *   prev      float32 [64]: the last `smoothed`, with the running mean of the betas in 51:61
+ *   vel       float32 [64]: the speed estimates -- w^ in 0:3, the fingers' in 6:51, the camera's in 61:64, the rest 0
+ *   n_shape, age, run, count   int32: usable frames averaged into the shape; frames since the last update (0 = never initialised, saturating);
+ *             consecutive updates; frames counted into the measures
+ * dir_mano_para_smooth_state_bytes is a pure host function and returns the row size.
+ *
+ * Per row, in this order.  Float32 arithmetic, every operation rounded on its own (`fp contract` is OFF in step 0's root matrix, in steps 4 and 5 and in
+ * the Rodrigues routine; it is the compiler's default, as in mano.hip, in the PCA product and in step 6 outside Rodrigues); sums of three products are
+ * ((p0 + p1) + p2); dt, 2 pi dt and alpha(d_cutoff) are computed in double and rounded once, as in dir_one_euro_step.
+ *   0. inputs, exactly as mano_forward_kernel forms them: R_x = the robust-6D root matrix of para[0:6] and its reflection flag (det < 0);
+ *      a_x[45] = hands_mean + comps . para[6:51] (one fmaf chain per component, k ascending); b_x = para[51:61]; c_x = cam_px.
+ *   1. usable iff valid is NULL or valid[b] != 0, the 61 components read and the 3 camera values are finite, and R_x is not a reflection.
+ *   2. not usable: (R_y, a_y, b_y, c_y) = (R_x, a_x, b_x, c_x) and six = para[0:6] bit for bit, so the forward output is dir_mano_forward's at
+ *      para (a NaN propagates); age += 1 if age > 0; run = 0; updated = 0; nothing else in the state changes.
+ *   3. initialise, when usable and age == 0 or age > max_gap (or the break of step 4): R_y = R_x with six = para[0:6], a_y = a_x, c_y = c_x;
+ *      every speed estimate = 0; age = 1, run = 1, updated = 2; shape as in step 5.
+ *   4. update.  dt = age / fps, alpha(fc) = 1 / (1 + 1 / ((2 pi dt) fc)).
+ *      root:    R_y1 = robust6D(prev six) (the same routine: the bits of the last frame's R_y);  D = R_y1^T R_x, D_ij = sum_k R_y1[k][i] R_x[k][j];
+ *               s = 0.5 (D21 - D12, D02 - D20, D10 - D01);  c = 0.5 (((D00 + D11) + D22) - 1);  n = sqrt((s0 s0 + s1 s1) + s2 s2).
+ *               n <= 1e-6 and c < 0: the relative rotation is about pi and its axis undetermined -- the row is a BREAK and goes to step 3.
+ *               w = s when n <= 1e-6, else k s with k = atan2(n, c) / n.
+ *               per component dx = w / dt, w^ = w^ + alpha(d_cutoff) (dx - w^);  v2 = ((0 + w^0 w^0) + w^1 w^1) + w^2 w^2;
+ *               fc = min_cutoff + beta (rot_speed_scale sqrt(v2));  E = the forward's Rodrigues-by-quaternion routine at v = alpha(fc) w (each
+ *               component multiplied first) WITHOUT its 1e-8 offset: angle = sqrt((v0 v0 + v1 v1) + v2 v2), E = I when that is 0 (the offset
+ *               would turn every step by 1e-8 rad about a fixed direction: the step response would not be the scalar filter's, nor the
+ *               rule equivariant);  R_tmp = R_y1 E;  six = columns 0 and 1 of R_tmp;  R_y = robust6D(six).
+ *               The state keeps six, not a matrix: the stored rotation cannot drift from orthonormal.
+ *      fingers: a is 15 points of 3 components under dir_one_euro_step's step 4 (one cutoff per joint), speed scale rot_speed_scale.
+ *      camera:  c is 3 points of 1 component under the same rule, speed scale cam_speed_scale.
+ *      then age = 1, run += 1 (saturating), updated = 1.
+ *   5. shape, on every usable row (initialising or updating; a gap never resets it, only zeroing the state does).  shape_frames == 0: b_y = b_x.
+ *      Otherwise, while n_shape < shape_frames: n_shape += 1; mean = b_x when n_shape == 1, else mean = mean + (b_x - mean) / n_shape;
+ *      and b_y = mean on every such row.  After shape_frames usable frames the mean is frozen: the betas that leave are the same bits every frame.
+ *   6. forward from (R_y, a_y, b_y): mano_forward_kernel's operations from its shape blend and Rodrigues stage on, with the tables' side, center_idx
+ *      and root_palm -> verts V, joints J (centred);  joints_px[j] = c_y[0] * J[j].xy + c_y[1:3].  With steps 2, 3 and 5 the first usable frame
+ *      of a sequence gives dir_mano_forward's verts and joints bit for bit (at any shape_frames: the mean of one frame is that frame).
+ *   7. measures, when run >= 3 after the update, in double (exact from the float32 values), per-lane partials in point order and then a fixed
+ *      tree: the second-difference jitter of dir_one_euro_step's step 5, raw (x = the raw_* stream; a NULL stream's sum stays 0) and filtered
+ *      (y = the outputs), for mesh_xyz, joint_xyz and joints_px;  bone flicker = sum over the 20 bones of | |J_c - J_p|_t - |J_c - J_p|_{t-1} |,
+ *      raw and filtered, the bones of finger f = 0..4 in output joint order being (0, 1+4f), (1+4f, 2+4f), (2+4f, 3+4f), (3+4f, 4+4f);  count += 1.
+ *   8. history shift on every usable row: y2 = y1, y1 = y, and per raw stream given x2 = x1, x1 = x.
+ * A (sequence, hand) gives the same bits in any slot of any batch and in either hand slot.
+ * A null pointer (valid and raw_* aside), B outside 1..DIR_CROP_MAX_BATCH, hands outside 1..2, fps, min_cutoff or d_cutoff <= 0, beta < 0,
+ * max_gap < 1, shape_frames < 0 or a negative speed scale gives DIR_E_INVALID and a message before any launch. */
+#define DIR_MANO_PARA_SMOOTH_FIELDS 11
+typedef struct dir_mano_para_smooth_hand {
+    const float* para;          /* [B,64]                                   */
+    const float* cam_px;        /* [B,3]                                    */
+    const float* raw_verts;     /* [B,778,3] or NULL                        */
+    const float* raw_joints;    /* [B,21,3] or NULL                         */
+    const float* raw_joints_px; /* [B,21,2] or NULL                         */
+    float* smoothed;            /* [B,64]: NOT a pd_mano_para (see above)   */
+    float* verts;               /* [B,778,3]                                */
+    float* joints;              /* [B,21,3]                                 */
+    float* joints_px;           /* [B,21,2]                                 */
+    int32_t* updated;           /* [B]                                      */
+    void* state;                /* B rows, in and out                       */
+} dir_mano_para_smooth_hand;
+typedef struct dir_mano_para_smooth_opts {
+    double fps, min_cutoff, beta, d_cutoff;
+    double rot_speed_scale;     /* rad/s -> the speed unit of beta (100: a guess of 100 mm per radian) */
+    double cam_speed_scale;
+    int32_t max_gap, shape_frames;
+} dir_mano_para_smooth_opts;
+long long dir_mano_para_smooth_state_bytes(long long* offsets);
+int dir_mano_para_smooth_step(const dir_mano_tables* tables_host, const dir_mano_para_smooth_hand* hands_host, const int32_t* valid,
+                              const dir_mano_para_smooth_opts* opts_host, int hands, int B, void* stream);
 
 #ifdef __cplusplus
 }
