@@ -7,16 +7,18 @@
 // Replaces manopth/manopth/manolayer.py:110-270 (+ rodrigues_layer.py:15-54, rot6d.py:26-60,
 // tensutils.py:6-42) and utils/utils.py:47-63 of the reference: ~4040 ATen op calls and a host sync
 // per call there, one launch here.
-#include "dir_common.h"
+//
+// The layer's arithmetic lives in mano_device.h; this kernel calls its per-thread functions and keeps its own table-streaming loops
+// (SPW samples share every table load, four vertex parts).
+#include "mano_device.h"
 
 #include <stdlib.h>
 
 namespace {
 
-constexpr int NV = 778, NV3 = 2334, NV3P = 2336, NJ = 16, NTHR = 640;   // table rows padded to 2336 floats (16-B aligned)
+using namespace dir::mano;
 
-__constant__ int kReorderJ[21] = {0, 13, 14, 15, 16, 1, 2, 3, 17, 4, 5, 6, 18, 10, 11, 12, 19, 7, 8, 9, 20};
-__constant__ int kTips[2][5] = {{745, 317, 444, 556, 673}, {745, 317, 445, 556, 673}};
+constexpr int NTHR = 640;
 
 struct ManoHand {
     dir_mano_tables t;
@@ -26,14 +28,6 @@ struct ManoHand {
     float* verts; float* joints; float* joint_uv; float* mesh_uv; int32_t* flags;
 };
 struct ManoArgs { ManoHand h[2]; long long* stamps; int B, hands, parts; };   // stamps: DIR_STAMPS=mano (tuning aid, else NULL)
-
-__device__ __forceinline__ void normalize3(float& x, float& y, float& z) {
-    // rot6d.py:54-60: v / max(|v|, 1e-8).  No FMA contraction: the robust-6D construction is
-    // ill-conditioned for near-parallel inputs (x - y tiny), so follow the reference's op sequence exactly.
-#pragma clang fp contract(off)
-    float m = fmaxf(sqrtf(x * x + y * y + z * z), 1e-8f);
-    x /= m; y /= m; z /= m;
-}
 
 // XCD-aware 1-D grid: a (hand, vertex part) combination lives on ONE XCD (8 / (hands * parts) XCDs each, samples dealt among them), so
 // each XCD's L2 holds only that combination's slice of the blend-shape tables -- with hands = 2, parts = 4 exactly one slice per XCD.
@@ -92,11 +86,7 @@ __global__ __launch_bounds__(THREADS) void mano_forward_kernel(ManoArgs args) {
     // ---- PCA coefficients -> axis angle (manolayer.py:131-144) ; shape blend (manolayer.py:180-182)
 #pragma unroll
     for (int s_ = 0; s_ < SPW; ++s_)
-        if (tid < 45) {
-            float acc = 0.f;
-            for (int k = 0; k < 45; ++k) acc = fmaf(s_pose[s_][6 + k], a.t.comps[k * 45 + tid], acc);
-            s_full[s_][tid] = a.t.hands_mean[tid] + acc;
-        }
+        if (tid < 45) s_full[s_][tid] = pca_axis_angle(a.t, s_pose[s_] + 6, tid);
     for (int i = f_lo + tid; i < f_hi; i += nthr) {
         float acc[SPW];
 #pragma unroll
@@ -111,68 +101,22 @@ __global__ __launch_bounds__(THREADS) void mano_forward_kernel(ManoArgs args) {
 #pragma unroll
         for (int s_ = 0; s_ < SPW; ++s_) s_v[s_][i] = acc[s_] + vt;
     }
-    if (tid >= 64 && tid < 64 + SPW) {
-        // robust 6D -> rotation (rot6d.py:26-51): columns (x', y', z)
-#pragma clang fp contract(off)
+    if (tid >= 64 && tid < 64 + SPW) {   // ---- robust 6D root
         const int s_ = tid - 64;
-        float x0 = s_pose[s_][0], x1 = s_pose[s_][1], x2 = s_pose[s_][2], y0 = s_pose[s_][3], y1 = s_pose[s_][4], y2 = s_pose[s_][5];
-        normalize3(x0, x1, x2);
-        normalize3(y0, y1, y2);
-        float m0 = x0 + y0, m1 = x1 + y1, m2 = x2 + y2;
-        float o0 = x0 - y0, o1 = x1 - y1, o2 = x2 - y2;
-        normalize3(m0, m1, m2);
-        normalize3(o0, o1, o2);
-        x0 = m0 + o0; x1 = m1 + o1; x2 = m2 + o2;
-        y0 = m0 - o0; y1 = m1 - o1; y2 = m2 - o2;
-        normalize3(x0, x1, x2);
-        normalize3(y0, y1, y2);
-        float z0 = x1 * y2 - x2 * y1, z1 = x2 * y0 - x0 * y2, z2 = x0 * y1 - x1 * y0;
-        normalize3(z0, z1, z2);
-        float* R = s_root[s_];
-        R[0] = x0; R[1] = y0; R[2] = z0;
-        R[3] = x1; R[4] = y1; R[5] = z1;
-        R[6] = x2; R[7] = y2; R[8] = z2;
-        if (a.flags && live(s_)) {
-            float det = x0 * (y1 * z2 - z1 * y2) - y0 * (x1 * z2 - z1 * x2) + z0 * (x1 * y2 - y1 * x2);
-            a.flags[bs(s_)] = det < 0.f ? 1 : 0;
-        }
+        int reflect;
+        robust6d(s_pose[s_], s_root[s_], reflect);
+        if (a.flags && live(s_)) a.flags[bs(s_)] = reflect;
     }
     __syncthreads(); stamp();
 
-    // ---- Rodrigues via quaternion (rodrigues_layer.py:43-54, 15-40)
+    // ---- Rodrigues via quaternion ; joint regression from the shaped template
     if (tid < 15 * SPW) {
-#pragma clang fp contract(off)
         const int s_ = tid / 15, jt = tid - 15 * s_;
-        float vx = s_full[s_][3 * jt], vy = s_full[s_][3 * jt + 1], vz = s_full[s_][3 * jt + 2];
-        float ex = vx + 1e-8f, ey = vy + 1e-8f, ez = vz + 1e-8f;
-        float angle = sqrtf(ex * ex + ey * ey + ez * ez);
-        float ax = vx / angle, ay = vy / angle, az = vz / angle;
-        float half = angle * 0.5f;
-        float w = cosf(half), sn = sinf(half);
-        float x = sn * ax, y = sn * ay, z = sn * az;
-        float qn = sqrtf(w * w + x * x + y * y + z * z);
-        w /= qn; x /= qn; y /= qn; z /= qn;
-        float w2 = w * w, x2 = x * x, y2 = y * y, z2 = z * z;
-        float wx = w * x, wy = w * y, wz = w * z, xy = x * y, xz = x * z, yz = y * z;
-        float* R = s_rot[s_] + 9 * jt;
-        R[0] = w2 + x2 - y2 - z2; R[1] = 2 * xy - 2 * wz;     R[2] = 2 * wy + 2 * xz;
-        R[3] = 2 * wz + 2 * xy;   R[4] = w2 - x2 + y2 - z2;   R[5] = 2 * yz - 2 * wx;
-        R[6] = 2 * xz - 2 * wy;   R[7] = 2 * wx + 2 * yz;     R[8] = w2 - x2 - y2 + z2;
-#pragma unroll
-        for (int e = 0; e < 9; ++e) s_pm[s_][9 * jt + e] = R[e] - ((e == 0 || e == 4 || e == 8) ? 1.f : 0.f);
+        joint_rotation(s_full[s_] + 3 * jt, s_rot[s_] + 9 * jt, s_pm[s_] + 9 * jt);
     }
-    // ---- joint regression from the shaped template (manolayer.py:183).  J = Jreg (v_template + shapedirs beta) is
-    //      linear in beta: j_template = Jreg v_template [16,3] and j_shapedirs = Jreg shapedirs [16,3,10] are folded once
-    //      at pack time (fp64), replacing 48 dot products of length 778 per sample by 48 of length 10.
     if (tid >= 128 && tid < 128 + NJ * 3) {
-        const int o = tid - 128;
 #pragma unroll
-        for (int s_ = 0; s_ < SPW; ++s_) {
-            float acc = a.t.j_template[o];
-#pragma unroll
-            for (int k = 0; k < 10; ++k) acc = fmaf(a.t.j_shapedirs[o * 10 + k], s_beta[s_][k], acc);
-            s_J[s_][o] = acc;
-        }
+        for (int s_ = 0; s_ < SPW; ++s_) s_J[s_][tid - 128] = joint_regress(a.t, s_beta[s_], tid - 128);
     }
     __syncthreads(); stamp();
 
@@ -203,95 +147,32 @@ __global__ __launch_bounds__(THREADS) void mano_forward_kernel(ManoArgs args) {
     // ---- kinematic chain (manolayer.py:192-229): finger f owns joints 1+3f, 2+3f, 3+3f
     if (tid < 5 * SPW) {
         const int s_ = tid / 5, fg = tid - 5 * s_;
-        float A[12];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            A[4 * r + 0] = s_root[s_][3 * r + 0]; A[4 * r + 1] = s_root[s_][3 * r + 1]; A[4 * r + 2] = s_root[s_][3 * r + 2];
-            A[4 * r + 3] = s_J[s_][r];
-        }
-        if (fg == 0) {
-#pragma unroll
-            for (int e = 0; e < 12; ++e) s_A[s_][e] = A[e];
-        }
-        int parent = 0;
-        for (int l = 0; l < 3; ++l) {
-            const int j = 1 + 3 * fg + l;
-            const float* R = s_rot[s_] + 9 * (j - 1);
-            const float t0 = s_J[s_][3 * j] - s_J[s_][3 * parent], t1 = s_J[s_][3 * j + 1] - s_J[s_][3 * parent + 1],
-                        t2 = s_J[s_][3 * j + 2] - s_J[s_][3 * parent + 2];
-            float N[12];
-#pragma unroll
-            for (int r = 0; r < 3; ++r) {
-                const float a0 = A[4 * r], a1 = A[4 * r + 1], a2 = A[4 * r + 2], a3 = A[4 * r + 3];
-                N[4 * r + 0] = a0 * R[0] + a1 * R[3] + a2 * R[6];
-                N[4 * r + 1] = a0 * R[1] + a1 * R[4] + a2 * R[7];
-                N[4 * r + 2] = a0 * R[2] + a1 * R[5] + a2 * R[8];
-                N[4 * r + 3] = a0 * t0 + a1 * t1 + a2 * t2 + a3;
-            }
-#pragma unroll
-            for (int e = 0; e < 12; ++e) { A[e] = N[e]; s_A[s_][12 * j + e] = N[e]; }
-            parent = j;
-        }
+        chain_finger(fg, s_root[s_], s_J[s_], s_rot[s_], s_A[s_]);
     }
     __syncthreads(); stamp();
-    if (tid < NJ * SPW) {   // A' = A - pack(A.[J;0])  (manolayer.py:231-234)
+    if (tid < NJ * SPW) {   // A' = A - pack(A.[J;0])
         const int s_ = tid / NJ, jt = tid - NJ * s_;
-        const float* A = s_A[s_] + 12 * jt;
-        const float j0 = s_J[s_][3 * jt], j1 = s_J[s_][3 * jt + 1], j2 = s_J[s_][3 * jt + 2];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            s_A2[s_][12 * jt + 4 * r + 0] = A[4 * r + 0];
-            s_A2[s_][12 * jt + 4 * r + 1] = A[4 * r + 1];
-            s_A2[s_][12 * jt + 4 * r + 2] = A[4 * r + 2];
-            s_A2[s_][12 * jt + 4 * r + 3] = A[4 * r + 3] - (A[4 * r] * j0 + A[4 * r + 1] * j1 + A[4 * r + 2] * j2);
-        }
+        a_prime(jt, s_A[s_], s_J[s_], s_A2[s_]);
     }
     __syncthreads(); stamp();
 
-    // ---- linear blend skinning (manolayer.py:236-246): T = sum_k w[v][k] A'[k]; vert = T.[v_posed;1]
+    // ---- linear blend skinning (manolayer.py:236-246): T = sum_k w[v][k] A'[k]; vert = T.[v_posed;1], the weights loaded once for the SPW samples
     for (int v = v_lo + tid; v < v_hi; v += nthr) {
-        const float4* wp = reinterpret_cast<const float4*>(a.t.weights + 16 * v);
         float w[16];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            float4 t4 = wp[q];
-            w[4 * q] = t4.x; w[4 * q + 1] = t4.y; w[4 * q + 2] = t4.z; w[4 * q + 3] = t4.w;
-        }
+        load_weights(a.t.weights, v, w);
 #pragma unroll
         for (int s_ = 0; s_ < SPW; ++s_) {
             float T[12];
-#pragma unroll
-            for (int e = 0; e < 12; ++e) T[e] = 0.f;
-#pragma unroll
-            for (int k = 0; k < 16; ++k) {                       // A'[k] as three 16-byte LDS reads (was 12 scalar reads; same fmaf order)
-                const float4* ak = reinterpret_cast<const float4*>(s_A2[s_] + 12 * k);
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    const float4 t4 = ak[r];
-                    T[4 * r] = fmaf(t4.x, w[k], T[4 * r]); T[4 * r + 1] = fmaf(t4.y, w[k], T[4 * r + 1]);
-                    T[4 * r + 2] = fmaf(t4.z, w[k], T[4 * r + 2]); T[4 * r + 3] = fmaf(t4.w, w[k], T[4 * r + 3]);
-                }
-            }
-            const float x = s_v[s_][3 * v], y = s_v[s_][3 * v + 1], z = s_v[s_][3 * v + 2];
-            s_v[s_][3 * v + 0] = T[0] * x + T[1] * y + T[2] * z + T[3];
-            s_v[s_][3 * v + 1] = T[4] * x + T[5] * y + T[6] * z + T[7];
-            s_v[s_][3 * v + 2] = T[8] * x + T[9] * y + T[10] * z + T[11];
+            blend(w, s_A2[s_], T);
+            skin_vertex(T, s_v[s_], s_v[s_], v);
         }
     }
     __syncthreads(); stamp();
 
-    // ---- joints: 16 chain joints + 5 fingertip vertices, reordered (manolayer.py:247-259)
+    // ---- joints: 16 chain joints + 5 fingertip vertices, reordered
     if (tid < 21 * SPW) {
         const int s_ = tid / 21, jt = tid - 21 * s_;
-        const int src = kReorderJ[jt];
-        const float* sv = s_v[s_];
-        float x, y, z;
-        if (src == 0 && a.t.root_palm) {
-            x = (sv[3 * 95] + sv[3 * 22]) / 2; y = (sv[3 * 95 + 1] + sv[3 * 22 + 1]) / 2;
-            z = (sv[3 * 95 + 2] + sv[3 * 22 + 2]) / 2;
-        } else if (src < 16) { x = s_A[s_][12 * src + 3]; y = s_A[s_][12 * src + 7]; z = s_A[s_][12 * src + 11]; }
-        else { const int v = kTips[a.t.side][src - 16]; x = sv[3 * v]; y = sv[3 * v + 1]; z = sv[3 * v + 2]; }
-        s_jtr[s_][3 * jt] = x; s_jtr[s_][3 * jt + 1] = y; s_jtr[s_][3 * jt + 2] = z;
+        joint_source(a.t.side, a.t.root_palm, jt, s_A[s_], s_v[s_], s_jtr[s_]);
     }
     __syncthreads(); stamp();
     if (tid < 3 * SPW) { const int s_ = tid / 3, c = tid - 3 * s_; s_c[s_][c] = a.t.center_idx >= 0 ? s_jtr[s_][3 * a.t.center_idx + c] : 0.f; }   // manolayer.py:261-265
@@ -361,15 +242,9 @@ static void launch_mano(const ManoArgs& a0, int B, int hands, hipStream_t s) {
 static int check_hand(const dir_mano_tables* t, const float* pose, int pose_stride, const float* betas,
                       int betas_stride, const float* cam, int cam_stride, float* verts, float* joints) {
     DIR_REQUIRE(t && pose && betas && verts && joints, "dir_mano_forward: null pointer");
-    DIR_REQUIRE(t->shapedirs_t && t->posedirs_t && t->v_template && t->j_template && t->j_shapedirs && t->weights &&
-                    t->hands_mean && t->comps, "dir_mano_forward: null table");
     DIR_REQUIRE(pose_stride >= 51 && betas_stride >= 10, "dir_mano_forward: bad stride");
-    DIR_REQUIRE(t->side == 0 || t->side == 1, "dir_mano_forward: side must be 0 (right) or 1 (left)");
-    DIR_REQUIRE(t->center_idx >= -1 && t->center_idx < 21, "dir_mano_forward: center_idx out of range");
     DIR_REQUIRE(cam == nullptr || cam_stride >= 3, "dir_mano_forward: bad cam stride");
-    DIR_REQUIRE(((uintptr_t)t->posedirs_t & 15) == 0 && ((uintptr_t)t->weights & 15) == 0,
-                "dir_mano_forward: posedirs_t / weights must be 16-byte aligned");
-    return DIR_OK;
+    return dir::mano::check_mano_tables(*t, "dir_mano_forward");
 }
 
 extern "C" int dir_mano_forward(const dir_mano_tables* t, const float* pose, int pose_stride, const float* betas,

@@ -8,16 +8,18 @@
 //                             scalar work (lane 64 the root, lanes 0..14 the fingers, 16..18 the camera, 32..41 the shape); the whole
 //                             workgroup does the blend shapes, the skinning, the history shift and the reductions of the measures.
 //
-// The forward body restates mano.hip operation for operation, as mano_fit.hip does (a first usable frame gives dir_mano_forward's bits); the
+// The forward is mano_device.h's phases, the ones mano.hip runs (a first usable frame gives dir_mano_forward's bits), skinning in place; the
 // One-Euro arithmetic restates smooth.hip's.  No atomics, no workspace, no flags between workgroups, vector stores only: a (sequence, hand)
 // gives the same bits in any slot of any batch and in either hand slot.
 #include <math.h>
 
-#include "dir_common.h"
+#include "mano_device.h"
 
 namespace {
 
-constexpr int NV = 778, NV3 = 2334, NV3P = 2336, NJ = 16, BT = 256;
+using namespace dir::mano;
+using dir::finite;
+
 constexpr int AGE_MAX = 1 << 30;                          // `age` and `run` saturate here
 constexpr int O_J = NV3, O_PX = NV3 + 63;                 // a history row: verts [2334] | joints [63] | joints_px [42] (2439 floats, padded to 2440)
 constexpr long long HIST = 2440 * 4;
@@ -26,9 +28,6 @@ constexpr long long HIST = 2440 * 4;
 constexpr long long S_MEASURES = 0, S_Y1 = 64, S_Y2 = S_Y1 + HIST, S_X1 = S_Y2 + HIST, S_X2 = S_X1 + HIST, S_PREV = S_X2 + HIST, S_VEL = S_PREV + 256,
                     S_NSHAPE = S_VEL + 256, S_AGE = S_NSHAPE + 4, S_RUN = S_AGE + 4, S_COUNT = S_RUN + 4, S_ROW = S_COUNT + 4;
 static_assert(S_ROW % 16 == 0 && S_ROW == 39632, "state row");
-
-__constant__ int kReorderJs[21] = {0, 13, 14, 15, 16, 1, 2, 3, 17, 4, 5, 6, 18, 10, 11, 12, 19, 7, 8, 9, 20};
-__constant__ int kTipss[2][5] = {{745, 317, 444, 556, 673}, {745, 317, 445, 556, 673}};
 
 struct SmoothArgs {
     dir_mano_tables t[2];
@@ -39,69 +38,9 @@ struct SmoothArgs {
     int max_gap, shape_frames;
 };
 
-__device__ __forceinline__ bool finite(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
-
 __device__ __forceinline__ float alpha(float r, float fc) {         // smooth.hip: r = 2 pi dt
 #pragma clang fp contract(off)
     return 1.f / (1.f + 1.f / (r * fc));
-}
-
-__device__ __forceinline__ void normalize3s(float& x, float& y, float& z) {      // mano.hip: normalize3
-#pragma clang fp contract(off)
-    const float m = fmaxf(sqrtf(x * x + y * y + z * z), 1e-8f);
-    x /= m; y /= m; z /= m;
-}
-
-// mano.hip's robust 6D -> rotation (row major, columns x', y', z) and its reflection flag
-__device__ __forceinline__ void robust6d(const float* p, float* R, int& reflect) {
-#pragma clang fp contract(off)
-    float x0 = p[0], x1 = p[1], x2 = p[2], y0 = p[3], y1 = p[4], y2 = p[5];
-    normalize3s(x0, x1, x2);
-    normalize3s(y0, y1, y2);
-    float m0 = x0 + y0, m1 = x1 + y1, m2 = x2 + y2;
-    float o0 = x0 - y0, o1 = x1 - y1, o2 = x2 - y2;
-    normalize3s(m0, m1, m2);
-    normalize3s(o0, o1, o2);
-    x0 = m0 + o0; x1 = m1 + o1; x2 = m2 + o2;
-    y0 = m0 - o0; y1 = m1 - o1; y2 = m2 - o2;
-    normalize3s(x0, x1, x2);
-    normalize3s(y0, y1, y2);
-    float z0 = x1 * y2 - x2 * y1, z1 = x2 * y0 - x0 * y2, z2 = x0 * y1 - x1 * y0;
-    normalize3s(z0, z1, z2);
-    R[0] = x0; R[1] = y0; R[2] = z0;
-    R[3] = x1; R[4] = y1; R[5] = z1;
-    R[6] = x2; R[7] = y2; R[8] = z2;
-    const float det = x0 * (y1 * z2 - z1 * y2) - y0 * (x1 * z2 - z1 * x2) + z0 * (x1 * y2 - y1 * x2);
-    reflect = det < 0.f ? 1 : 0;
-}
-
-// mano.hip's Rodrigues via quaternion.  OFFSET = true: the forward's own (angle = |v + 1e-8|); false: the root step's E, angle = |v| exactly and
-// E = I at |v| == 0 -- the 1e-8 offset would bias every step by 1e-8 rad about a fixed direction (the step response is then not the scalar filter's)
-template <bool OFFSET> __device__ __forceinline__ void rodrigues(float vx, float vy, float vz, float* R) {
-#pragma clang fp contract(off)
-    float angle;
-    if (OFFSET) {
-        float ex = vx + 1e-8f, ey = vy + 1e-8f, ez = vz + 1e-8f;
-        angle = sqrtf(ex * ex + ey * ey + ez * ez);
-    } else {
-        angle = sqrtf(vx * vx + vy * vy + vz * vz);
-        if (angle == 0.f) {
-#pragma unroll
-            for (int e = 0; e < 9; ++e) R[e] = (e == 0 || e == 4 || e == 8) ? 1.f : 0.f;
-            return;
-        }
-    }
-    float ax = vx / angle, ay = vy / angle, az = vz / angle;
-    float half = angle * 0.5f;
-    float w = cosf(half), sn = sinf(half);
-    float x = sn * ax, y = sn * ay, z = sn * az;
-    float qn = sqrtf(w * w + x * x + y * y + z * z);
-    w /= qn; x /= qn; y /= qn; z /= qn;
-    float w2 = w * w, x2 = x * x, y2 = y * y, z2 = z * z;
-    float wx = w * x, wy = w * y, wz = w * z, xy = x * y, xz = x * z, yz = y * z;
-    R[0] = w2 + x2 - y2 - z2; R[1] = 2 * xy - 2 * wz;     R[2] = 2 * wy + 2 * xz;
-    R[3] = 2 * wz + 2 * xy;   R[4] = w2 - x2 + y2 - z2;   R[5] = 2 * yz - 2 * wx;
-    R[6] = 2 * xz - 2 * wy;   R[7] = 2 * wx + 2 * yz;     R[8] = w2 - x2 - y2 + z2;
 }
 
 // One-Euro on one point of D components (smooth.hip's walk_segment): x, the last output y1 and the speed estimate h, in LDS; y and h are updated
@@ -157,21 +96,19 @@ __device__ __forceinline__ double bone_length(const float* j, int p, int c) {
 __global__ __launch_bounds__(BT) void mano_para_smooth_kernel(SmoothArgs args) {
     const dir_mano_tables& T = args.t[blockIdx.y];
     const dir_mano_para_smooth_hand& a = args.h[blockIdx.y];
+    const int side = T.side, center = T.center_idx, root_palm = T.root_palm;       // read once, here (mano_device.h, layer 2)
     __shared__ float s_v[NV3P];          // v_shaped -> v_posed -> skinned -> centred vertices (in place)
     __shared__ float s_in[64];           // para[0:61] | cam_px
     __shared__ float s_prev[64];         // the state's last output: six | a_y1 | mean betas | c_y1
     __shared__ float s_vel[64];          // the state's speed estimates: w^ [3], 0 [3] | fingers [45] | unused [10] | camera [3]
     __shared__ float s_out[64];          // `smoothed`: six | a_y | b_y | c_y
-    __shared__ float s_rot[135], s_pm[135], s_root[9], s_J[48];
-    __shared__ float s_A[NJ * 12];
-    __shared__ __attribute__((aligned(16))) float s_A2[NJ * 12];
-    __shared__ float s_jtr[63], s_c[3], s_jo[63], s_px[42];
+    DIR_MANO_LDS(L, s);
+    __shared__ float s_jo[63], s_px[42];
     __shared__ double s_red[8][BT];
     __shared__ int s_reflect, s_break;
 
     const int tid = threadIdx.x;
     const size_t b = blockIdx.x;
-    const int center = T.center_idx;
     const float* s_full = s_out + 6;
     const float* s_beta = s_out + 51;
     unsigned char* st = static_cast<unsigned char*>(a.state) + b * (size_t)S_ROW;
@@ -195,14 +132,10 @@ __global__ __launch_bounds__(BT) void mano_para_smooth_kernel(SmoothArgs args) {
     const int age = *age_p, run = *run_p, n_shape = *nshape_p;      // read by every lane; lane 0 writes them behind the last barrier
     bad = __syncthreads_or(bad);
 
-    if (tid < 45) {                                                  // a_x = hands_mean + comps . pca (mano.hip)
-        float acc = 0.f;
-        for (int k = 0; k < 45; ++k) acc = fmaf(s_in[6 + k], T.comps[k * 45 + tid], acc);
-        s_out[6 + tid] = T.hands_mean[tid] + acc;
-    }
+    if (tid < 45) s_out[6 + tid] = pca_axis_angle(T, s_in + 6, tid);       // a_x = hands_mean + comps . pca
     if (tid == 64) {                                                 // R_x and its reflection flag
         int refl;
-        robust6d(s_in, s_root, refl);
+        robust6d(s_in, L.root, refl);
         s_reflect = refl;
     }
     if (tid >= 128 && tid < 134) s_out[tid - 128] = s_in[tid - 128];            // six, betas and camera pass through until a filter replaces them
@@ -225,7 +158,7 @@ __global__ __launch_bounds__(BT) void mano_para_smooth_kernel(SmoothArgs args) {
 #pragma unroll
         for (int i = 0; i < 3; ++i)
 #pragma unroll
-            for (int j = 0; j < 3; ++j) D[3 * i + j] = Rp[i] * s_root[j] + Rp[3 + i] * s_root[3 + j] + Rp[6 + i] * s_root[6 + j];
+            for (int j = 0; j < 3; ++j) D[3 * i + j] = Rp[i] * L.root[j] + Rp[3 + i] * L.root[3 + j] + Rp[6 + i] * L.root[6 + j];
         const float s0 = 0.5f * (D[7] - D[5]), s1 = 0.5f * (D[2] - D[6]), s2 = 0.5f * (D[3] - D[1]);
         const float c = 0.5f * (((D[0] + D[4]) + D[8]) - 1.f);
         const float n = sqrtf(s0 * s0 + s1 * s1 + s2 * s2);
@@ -248,14 +181,15 @@ __global__ __launch_bounds__(BT) void mano_para_smooth_kernel(SmoothArgs args) {
             const float fc = args.min_cutoff + args.beta * (args.rot_scale * sqrtf(v2));
             const float al = alpha(r, fc);
             float E[9], Rt[9];
-            rodrigues<false>(al * w[0], al * w[1], al * w[2], E);
+            const float step[3] = {al * w[0], al * w[1], al * w[2]};
+            rodrigues_quat<false>(step, E);                          // angle = |v| exactly, E = I at 0: see rodrigues_quat
 #pragma unroll
             for (int i = 0; i < 3; ++i)
 #pragma unroll
                 for (int j = 0; j < 3; ++j) Rt[3 * i + j] = Rp[3 * i] * E[j] + Rp[3 * i + 1] * E[3 + j] + Rp[3 * i + 2] * E[6 + j];
             s_out[0] = Rt[0]; s_out[1] = Rt[3]; s_out[2] = Rt[6];   // six = columns 0 and 1 of R_y1 . E
             s_out[3] = Rt[1]; s_out[4] = Rt[4]; s_out[5] = Rt[7];
-            robust6d(s_out, s_root, refl);                           // R_y
+            robust6d(s_out, L.root, refl);                           // R_y
         }
     }
     __syncthreads();
@@ -287,125 +221,27 @@ __global__ __launch_bounds__(BT) void mano_para_smooth_kernel(SmoothArgs args) {
         }
     }
 
-    // ================================================================ step 6: the forward from (R_y, a_y, b_y), as mano_forward_kernel from its shape blend on
-    for (int i = tid; i < NV3; i += BT) {
-        float acc = 0.f;
-#pragma unroll
-        for (int k = 0; k < 10; ++k) acc = fmaf(T.shapedirs_t[k * NV3P + i], s_beta[k], acc);
-        s_v[i] = acc + T.v_template[i];
-    }
-    if (tid < 15) {
-        float* R = s_rot + 9 * tid;
-        rodrigues<true>(s_full[3 * tid], s_full[3 * tid + 1], s_full[3 * tid + 2], R);
-#pragma unroll
-        for (int e = 0; e < 9; ++e) s_pm[9 * tid + e] = R[e] - ((e == 0 || e == 4 || e == 8) ? 1.f : 0.f);
-    }
-    if (tid >= 128 && tid < 128 + NJ * 3) {
-        const int o = tid - 128;
-        float acc = T.j_template[o];
-#pragma unroll
-        for (int k = 0; k < 10; ++k) acc = fmaf(T.j_shapedirs[o * 10 + k], s_beta[k], acc);
-        s_J[o] = acc;
-    }
+    // ================================================================ step 6: the forward from (R_y, a_y, b_y): mano_device.h's phases from the shape blend on
+    shape_blend(T, s_beta, s_v, tid);
+    joint_rotations(L, s_full, tid);
+    joint_regression(L, T, s_beta, tid);
     __syncthreads();
-    for (int c4 = tid; c4 < NV3P / 4; c4 += BT) {
-        const float4* pd = reinterpret_cast<const float4*>(T.posedirs_t) + c4;
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll 9
-        for (int k = 0; k < 135; ++k) {
-            const float4 p = pd[k * (NV3P / 4)];
-            const float w = s_pm[k];
-            acc.x = fmaf(p.x, w, acc.x); acc.y = fmaf(p.y, w, acc.y); acc.z = fmaf(p.z, w, acc.z); acc.w = fmaf(p.w, w, acc.w);
-        }
-        const int i = 4 * c4;
-        s_v[i] += acc.x; s_v[i + 1] += acc.y;
-        if (i + 2 < NV3) { s_v[i + 2] += acc.z; s_v[i + 3] += acc.w; }
-    }
-    if (tid < 5) {
-        float A[12];
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            A[4 * q + 0] = s_root[3 * q + 0]; A[4 * q + 1] = s_root[3 * q + 1]; A[4 * q + 2] = s_root[3 * q + 2];
-            A[4 * q + 3] = s_J[q];
-        }
-        if (tid == 0) {
-#pragma unroll
-            for (int e = 0; e < 12; ++e) s_A[e] = A[e];
-        }
-        int parent = 0;
-        for (int l = 0; l < 3; ++l) {
-            const int j = 1 + 3 * tid + l;
-            const float* R = s_rot + 9 * (j - 1);
-            const float t0 = s_J[3 * j] - s_J[3 * parent], t1 = s_J[3 * j + 1] - s_J[3 * parent + 1], t2 = s_J[3 * j + 2] - s_J[3 * parent + 2];
-            float N[12];
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                const float a0 = A[4 * q], a1 = A[4 * q + 1], a2 = A[4 * q + 2], a3 = A[4 * q + 3];
-                N[4 * q + 0] = a0 * R[0] + a1 * R[3] + a2 * R[6];
-                N[4 * q + 1] = a0 * R[1] + a1 * R[4] + a2 * R[7];
-                N[4 * q + 2] = a0 * R[2] + a1 * R[5] + a2 * R[8];
-                N[4 * q + 3] = a0 * t0 + a1 * t1 + a2 * t2 + a3;
-            }
-#pragma unroll
-            for (int e = 0; e < 12; ++e) { A[e] = N[e]; s_A[12 * j + e] = N[e]; }
-            parent = j;
-        }
-    }
+    pose_blend(L, T, s_v, tid);
+    chain(L, tid);
     __syncthreads();
-    if (tid < NJ) {
-        const float* A = s_A + 12 * tid;
-        const float j0 = s_J[3 * tid], j1 = s_J[3 * tid + 1], j2 = s_J[3 * tid + 2];
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            s_A2[12 * tid + 4 * q + 0] = A[4 * q + 0];
-            s_A2[12 * tid + 4 * q + 1] = A[4 * q + 1];
-            s_A2[12 * tid + 4 * q + 2] = A[4 * q + 2];
-            s_A2[12 * tid + 4 * q + 3] = A[4 * q + 3] - (A[4 * q] * j0 + A[4 * q + 1] * j1 + A[4 * q + 2] * j2);
-        }
-    }
+    a_primes(L, tid);
     __syncthreads();
-    for (int v = tid; v < NV; v += BT) {
-        const float4* wp = reinterpret_cast<const float4*>(T.weights + 16 * v);
-        float w[16];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { const float4 t4 = wp[q]; w[4 * q] = t4.x; w[4 * q + 1] = t4.y; w[4 * q + 2] = t4.z; w[4 * q + 3] = t4.w; }
-        float Tm[12];
-#pragma unroll
-        for (int e = 0; e < 12; ++e) Tm[e] = 0.f;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const float4* ak = reinterpret_cast<const float4*>(s_A2 + 12 * k);
-#pragma unroll
-            for (int q = 0; q < 3; ++q) {
-                const float4 t4 = ak[q];
-                Tm[4 * q] = fmaf(t4.x, w[k], Tm[4 * q]); Tm[4 * q + 1] = fmaf(t4.y, w[k], Tm[4 * q + 1]);
-                Tm[4 * q + 2] = fmaf(t4.z, w[k], Tm[4 * q + 2]); Tm[4 * q + 3] = fmaf(t4.w, w[k], Tm[4 * q + 3]);
-            }
-        }
-        const float x = s_v[3 * v], y = s_v[3 * v + 1], z = s_v[3 * v + 2];
-        s_v[3 * v + 0] = Tm[0] * x + Tm[1] * y + Tm[2] * z + Tm[3];
-        s_v[3 * v + 1] = Tm[4] * x + Tm[5] * y + Tm[6] * z + Tm[7];
-        s_v[3 * v + 2] = Tm[8] * x + Tm[9] * y + Tm[10] * z + Tm[11];
-    }
+    skinning(L, T, s_v, s_v, tid);
     __syncthreads();
-    if (tid < 21) {
-        const int src = kReorderJs[tid];
-        float x, y, z;
-        if (src == 0 && T.root_palm) {
-            x = (s_v[3 * 95] + s_v[3 * 22]) / 2; y = (s_v[3 * 95 + 1] + s_v[3 * 22 + 1]) / 2;
-            z = (s_v[3 * 95 + 2] + s_v[3 * 22 + 2]) / 2;
-        } else if (src < 16) { x = s_A[12 * src + 3]; y = s_A[12 * src + 7]; z = s_A[12 * src + 11]; }
-        else { const int v = kTipss[T.side][src - 16]; x = s_v[3 * v]; y = s_v[3 * v + 1]; z = s_v[3 * v + 2]; }
-        s_jtr[3 * tid] = x; s_jtr[3 * tid + 1] = y; s_jtr[3 * tid + 2] = z;
-    }
+    joints(L, side, root_palm, s_v, tid);
     __syncthreads();
-    if (tid < 3) s_c[tid] = center >= 0 ? s_jtr[3 * center + tid] : 0.f;
+    centre(L, center, tid);
     __syncthreads();
-    for (int i = tid; i < NV3; i += BT) s_v[i] = s_v[i] - s_c[i % 3];
-    if (tid < 63) s_jo[tid] = s_jtr[tid] - s_c[tid % 3];
+    for (int i = tid; i < NV3; i += BT) s_v[i] = s_v[i] - L.c[i % 3];
+    if (tid < 63) s_jo[tid] = L.jtr[tid] - L.c[tid % 3];
     if (tid >= 64 && tid < 64 + 42) {                                // joints_px = c_y[0] J.xy + c_y[1:3] (mano.hip's projection)
         const int i = tid - 64, j = i >> 1, c = i & 1;
-        s_px[i] = s_out[61] * (s_jtr[3 * j + c] - s_c[c]) + (c ? s_out[63] : s_out[62]);
+        s_px[i] = s_out[61] * (L.jtr[3 * j + c] - L.c[c]) + (c ? s_out[63] : s_out[62]);
     }
     __syncthreads();
 
@@ -485,12 +321,9 @@ extern "C" int dir_mano_para_smooth_step(const dir_mano_tables* tables_host, con
         const dir_mano_para_smooth_hand& x = hands_host[s];
         DIR_REQUIRE(x.para && x.cam_px && x.smoothed && x.verts && x.joints && x.joints_px && x.updated && x.state,
                     "dir_mano_para_smooth_step: null pointer (hand %d)", s);
-        DIR_REQUIRE(t.shapedirs_t && t.posedirs_t && t.v_template && t.j_template && t.j_shapedirs && t.weights && t.hands_mean && t.comps,
-                    "dir_mano_para_smooth_step: null table (hand %d)", s);
-        DIR_REQUIRE(t.side == 0 || t.side == 1, "dir_mano_para_smooth_step: side must be 0 (right) or 1 (left)");
-        DIR_REQUIRE(t.center_idx >= -1 && t.center_idx < 21, "dir_mano_para_smooth_step: center_idx out of range");
-        DIR_REQUIRE(((uintptr_t)t.posedirs_t & 15) == 0 && ((uintptr_t)t.weights & 15) == 0,
-                    "dir_mano_para_smooth_step: posedirs_t / weights must be 16-byte aligned");
+        char who[48];
+        snprintf(who, sizeof who, "dir_mano_para_smooth_step (hand %d)", s);
+        if (int rc = dir::mano::check_mano_tables(t, who)) return rc;
         DIR_REQUIRE(((uintptr_t)x.state & 15) == 0, "dir_mano_para_smooth_step: the state must be 16-byte aligned");
         a.t[h] = t;
         a.h[h] = x;

@@ -134,10 +134,10 @@ int dir_mano_backward_pair(const dir_mano_tables* tables_lr_host, const float* c
  * may hold NaN (a missing keypoint).
  *
  * One iteration, in this order, fp32 throughout (one launch runs all of them; one 256-thread workgroup per (sample, hand) keeps the hand in LDS):
- *   1. the forward at p, operation for operation dir_mano_forward's;
+ *   1. the forward at p: the device functions dir_mano_forward runs (csrc/mano_device.h holds the layer once, for every kernel that runs it);
  *   2. the cotangents gV = k_v (V - V*), gJ = (k_j c_j) (J_j - J*_j), gU = (k_uv d_j) (U_j - U*_j), 0 where selected out, with
  *      k_v = 2 w_verts / 778, k_j = 2 w_joints / 21, k_uv = 2 w_uv / 21 formed in double on the host and rounded to float once;
- *   3. g = dir_mano_backward_pair's gradient for these cotangents (same operations; 64-lane sums on DPP row operations, fixed order; with
+ *   3. g = dir_mano_backward_pair's gradient for these cotangents (the same device functions; 64-lane sums on DPP row operations, fixed order; with
  *      root_palm, which that entry point rejects, joint 0 = (v95 + v22) / 2 hands half its gradient to each of the two vertices);
  *   4. g[6:51] += (2 w_pca) p, then g[51:61] += (2 w_beta) p, then g += (2 w_init) (p - a), each product and sum rounded (no FMA contraction);
  *   5. Adam, step t = t0 + 1 .. t0 + iters, per component of group G (root 0:6, pca 6:51, betas 51:61, cam 61:64), no FMA contraction:

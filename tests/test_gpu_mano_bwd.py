@@ -89,6 +89,34 @@ def test_mano_backward_without_projection():
     assert np.abs(got[:, :61] - ref[:, :61]).max() / np.abs(ref).max() < 1e-5 and float(np.abs(got[:, 61:]).max()) == 0.0
 
 
+def test_mano_backward_refuses_a_misaligned_table():
+    """posedirs_t, then weights, 4 bytes off a 16-byte boundary (the kernel reads both as float4): DIR_E_INVALID naming the alignment, nothing launched, g untouched"""
+    import ctypes as C
+    from dir_amd import _capi
+    L = _capi.lib()
+    T, keep, _ = tables('right', 9)
+    para, cot = mano_grad_inputs('normal', 'right')
+    dp, gv = dev(para[:1]), dev(cot['verts'][:1])
+    out = torch.full((1, 64), 3.0, device='cuda')
+    off, off_w = _capi.ManoTables.from_buffer_copy(T), _capi.ManoTables.from_buffer_copy(T)
+    off.posedirs_t = T.posedirs_t + 4
+    off_w.weights = T.weights + 4
+    P1 = C.c_void_p * 1
+    call = lambda t: L.dir_mano_backward_pair((_capi.ManoTables * 1)(t), P1(dp.data_ptr()), 64, P1(dp.data_ptr() + 51 * 4), 64, None, 0,  # noqa: E731
+                                              P1(gv.data_ptr()), None, None, None, P1(out.data_ptr()), 64, P1(out.data_ptr() + 51 * 4), 64, None, 0, 1, 1,
+                                              _capi.stream_ptr())
+    L.dir_launch_log_reset()
+    for t in (off, off_w):
+        assert call(t) == -1 and b'dir_mano_backward_pair' in L.dir_last_error() and b'16-byte aligned' in L.dir_last_error()
+    buf = C.create_string_buffer(1024)
+    L.dir_launch_log_get(buf, 1024)
+    torch.cuda.synchronize()
+    assert buf.value == b'' and bool((out == 3.0).all())
+    assert call(T) == 0                                           # the same call with the table where it belongs
+    torch.cuda.synchronize()
+    assert bool((out[:, :61] != 3.0).all())
+
+
 def test_regressor_backward_chain_vs_reference_autograd(golden):
     """G14 = torch autograd through the reference's RegressorOffset (three Linears -> two MANO layers -> four projections).  HIP chain:
     dir_regress_forward -> dir_mano_backward_pair (cotangents of the MANO outputs -> g mano_para) -> dir_regress_backward (parameter
