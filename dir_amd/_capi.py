@@ -35,6 +35,14 @@ class ManoFitOpts(C.Structure):        # dir_mano_fit_opts
 MANO_FIT_STATE = 132     # DIR_MANO_FIT_STATE
 
 
+class ManoFitStartHand(C.Structure):   # dir_mano_fit_start_hand
+    _fields_ = [(n, C.c_void_p) for n in ('p0', 'p_out', 'verts_t', 'joints_t', 'joints_conf', 'uv_t', 'uv_conf', 'status', 'choice', 'info')]
+
+
+class ManoFitStartOpts(C.Structure):   # dir_mano_fit_start_opts
+    _fields_ = [(n, C.c_float) for n in ('w_verts', 'w_joints')] + [(n, C.c_int32) for n in ('root', 'cam', 'search')]
+
+
 class ConvDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         'B', 'H', 'W', 'Cin', 'in_cstride', 'in_coff', 'Cout', 'out_cstride', 'out_coff', 'res_cstride', 'res_coff',
@@ -173,7 +181,7 @@ class RenderLights(C.Structure):         # dir_render_lights
                 ('shininess', C.c_float)]
 
 
-ABI_VERSION = 53         # DIR_ABI_VERSION (include/dir_hip.h)
+ABI_VERSION = 54         # DIR_ABI_VERSION (include/dir_hip.h)
 DT_F32, DT_BF16, DT_F16X3, DT_F16X1, DT_F16X3P, DT_F16X1P, DT_F16 = 0, 1, 3, 4, 5, 6, 7      # DT_F16: f16 STORAGE (round 5)
 CONV_RELU, CONV_PRE_RELU = 1, 2
 
@@ -251,6 +259,7 @@ _SIGNATURES = {
     'dir_mano_forward_pair': (C.c_int, [C.POINTER(ManoTables), _p, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _i, _p]),
     'dir_mano_backward_pair': (C.c_int, [C.POINTER(ManoTables), _p, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _i, _p, _i, _p, _i, _i, _i, _p]),
     'dir_mano_fit': (C.c_int, [C.POINTER(ManoTables), C.POINTER(ManoFitHand), C.POINTER(ManoFitOpts), _i, _i, _p]),
+    'dir_mano_fit_start': (C.c_int, [C.POINTER(ManoTables), C.POINTER(ManoFitStartHand), C.POINTER(ManoFitStartOpts), _i, _i, _p]),
     'dir_regress_backward': (C.c_int, [_p] * 17 + [_i, _p]),
     'dir_gemm_f32': (C.c_int, [C.POINTER(GemmDesc), _p, _p, _p, _p, _p]),
     'dir_gemm_f32_grouped': (C.c_int, [C.POINTER(GemmDesc), C.POINTER(GemmGroups), _p, _p, _p, _p, _p]),

@@ -3,7 +3,7 @@
 
     python -m dir_amd.apps.fit_mano --model CKPT --targets T.npz --out O.npz [--iters 200] [--lr 0.1] [--lr_root --lr_pca --lr_betas --lr_cam]
                                     [--bs 256] [--center 0] [--cam_scale 1.0] [--w_verts 1e4 --w_joints 1e4 --w_uv 1 --w_pca 0 --w_beta 0
-                                    --w_init 0] [--ema]
+                                    --w_init 0] [--ema] [--start neutral|closed]
 
 The MANO tables come from the checkpoint (init_regressor.mano_layer_{left,right}.th_*), as in apps.predict.  T.npz holds, per side in
 (left, right), any of  verts_<side> [N,778,3],  joints_<side> [N,21,3] with joints_conf_<side> [N,21],  joint_uv_<side> [N,21,2] (the crop's
@@ -12,7 +12,11 @@ The MANO tables come from the checkpoint (init_regressor.mano_layer_{left,right}
 entry, which may then hold NaN.  A side with no target is left out.  O.npz holds para_<side> [N,64], the fitted verts_ / joints_ / joint_uv_<side>,
 mse_before_<side> and mse_after_<side> [N,3] (mean squared residual of the vertices, 3-D joints and 2-D joints, unweighted) and status_<side>
 [N] (bit 0 reflection, bit 1 non-finite input: passed through, bit 2 a step went non-finite: stopped there).  The last line printed is
-"N hands in T s".  The defaults are NOT tuned on real MANO tables or real keypoints.
+"N hands in T s".  --start closed (default neutral: the output is as without the flag): before the fit, dir_mano_fit_start turns the start's root onto 3-D
+targets by a rigid alignment (with 2-D targets alone: the best of the cube's 24 rotations) and fits its camera by least squares
+(utils/mano_fit.py start_mano), so targets rotated anywhere are reached and --cam_scale need not be guessed; the fit is anchored at the started
+parameters, and O.npz gains start_<side> [N,64], start_status_<side> [N] (8: the root was kept, 16: the camera was kept) and start_choice_<side>
+[N] (the rotation the 2-D search wrote, else -1).  The defaults are NOT tuned on real MANO tables or real keypoints.
 """
 import time
 
@@ -58,9 +62,9 @@ def tables_from_checkpoint(state, center=0, device='cuda'):
     return {s: pack_mano(sd, 'init_regressor.mano_layer_' + s, s, None if center < 0 else center, keep) for s in SIDES}, keep
 
 
-def fit_targets(tables, targets, iters=200, lr=0.1, weights=None, bs=256, cam_scale=1.0, device='cuda'):
-    """targets: read_targets' dict -> {side: {para, verts, joints, joint_uv, mse_before, mse_after, status}} (numpy).  Both sides with the same N go
-    through one launch per batch as a pair, otherwise one side at a time."""
+def fit_targets(tables, targets, iters=200, lr=0.1, weights=None, bs=256, cam_scale=1.0, device='cuda', start='neutral'):
+    """targets: read_targets' dict -> {side: {para, verts, joints, joint_uv, mse_before, mse_after, status}} (numpy; with start='closed' also start,
+    start_status, start_choice).  Both sides with the same N go through one launch per batch as a pair, otherwise one side at a time."""
     import torch
 
     from ..utils import mano_fit as MF
@@ -82,11 +86,18 @@ def fit_targets(tables, targets, iters=200, lr=0.1, weights=None, bs=256, cam_sc
                     w[k] = 0.0
                 else:
                     w.setdefault(k, MF.DEFAULT_WEIGHTS[k])
-            r = MF.fit_mano([tables[s] for s in grp] if len(grp) == 2 else tables[grp[0]], init if len(grp) == 2 else init[0], arg('verts'), arg('joints'),
-                            arg('joints_conf'), arg('joint_uv'), arg('uv_conf'), iters=iters, lr=lr, weights=w)
+            tabs, init = ([tables[s] for s in grp], init) if len(grp) == 2 else (tables[grp[0]], init[0])
+            anchor = st = None
+            if start == 'closed':
+                st = MF.start_mano(tabs, init, arg('verts'), arg('joints'), arg('joints_conf'), arg('joint_uv'), arg('uv_conf'), weights=w)
+                init = anchor = st.para
+            r = MF.fit_mano(tabs, init, arg('verts'), arg('joints'), arg('joints_conf'), arg('joint_uv'), arg('uv_conf'), iters=iters, lr=lr, weights=w, anchor=anchor)
             for h, s in enumerate(grp):
                 parts[s].append({k: (getattr(r, k)[h] if len(grp) == 2 else getattr(r, k)).cpu().numpy() for k in ('para', 'verts', 'joints', 'joint_uv', 'mse_before',
                                                                                                                     'mse_after', 'status')})
+                if st is not None:
+                    parts[s][-1].update({n: (getattr(st, k)[h] if len(grp) == 2 else getattr(st, k)).cpu().numpy()
+                                         for n, k in (('start', 'para'), ('start_status', 'status'), ('start_choice', 'choice'))})
         for s in grp:
             out[s] = {k: np.concatenate([p[k] for p in parts[s]]) for k in parts[s][0]}
     return out
@@ -112,6 +123,7 @@ def main(argv=None):
     ap.add_argument('--cam_scale', type=float, default=1.0, help='the camera scale of the cold start')
     for k, d in (('w_verts', None), ('w_joints', None), ('w_uv', None), ('w_pca', 0.0), ('w_beta', 0.0), ('w_init', 0.0)):
         ap.add_argument('--' + k, type=float, default=d)
+    ap.add_argument('--start', choices=('neutral', 'closed'), default='neutral', help='closed: root and camera of the start in closed form (dir_mano_fit_start)')
     opt = ap.parse_args(argv)
     if opt.bs < 1 or opt.iters < 0 or not -1 <= opt.center < 21:
         ap.error('--bs must be at least 1, --iters at least 0 and --center in -1 .. 20')
@@ -122,7 +134,7 @@ def main(argv=None):
     lr = {g: (getattr(opt, 'lr_' + g) if getattr(opt, 'lr_' + g) is not None else opt.lr) for g in ('root', 'pca', 'betas', 'cam')}
     weights = {k: getattr(opt, k) for k in ('w_verts', 'w_joints', 'w_uv', 'w_pca', 'w_beta', 'w_init') if getattr(opt, k) is not None}
     t0 = time.perf_counter()
-    res = fit_targets(tables, targets, opt.iters, lr, weights, opt.bs, opt.cam_scale)
+    res = fit_targets(tables, targets, opt.iters, lr, weights, opt.bs, opt.cam_scale, start=opt.start)
     torch.cuda.synchronize()
     sec = time.perf_counter() - t0
     np.savez(opt.out, **{'%s_%s' % (k, s): v for s, d in res.items() for k, v in d.items()})

@@ -368,3 +368,38 @@ def mano_fit(tables_lr, init_lr, verts=None, joints=None, joints_conf=None, join
         _capi.check(_capi.lib().dir_mano_fit((_capi.ManoTables * hands)(*tables_lr), (_capi.ManoFitHand * hands)(*hs), C.byref(opts), hands, B,
                                              _capi.stream_ptr()), 'dir_mano_fit')
     return res
+
+
+def mano_fit_start(tables_lr, init_lr, verts=None, joints=None, joints_conf=None, joint_uv=None, uv_conf=None, w_verts=0.0, w_joints=0.0, root=True, cam=True,
+                   search=True, para_out=None):
+    """dir_mano_fit_start (include/dir_hip.h, "MANO fitting: closed-form start").  Arguments as mano_fit's (lists with one tensor or None per hand;
+    para_out may hold the init tensors themselves).  -> list per hand of dicts para [B,64], status [B] int32, choice [B] int32, info [B,4]."""
+    import ctypes as C
+    hands = len(init_lr)
+    assert hands in (1, 2) and len(tables_lr) == hands
+    B, dev = init_lr[0].shape[0], init_lr[0].device
+
+    def per_hand(ts, shape, what):
+        ts = [None] * hands if ts is None else list(ts)
+        assert len(ts) == hands
+        for t in ts:
+            if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape and t.device == dev):
+                raise _capi.DirHipError('mano_fit_start: %s must be a contiguous float32 %s tensor on %s' % (what, list(shape), dev))
+        _capi.require_cuda(*ts)
+        return ts
+    init = per_hand(init_lr, (B, 64), 'init')
+    tv, tj, cj = per_hand(verts, (B, 778, 3), 'verts'), per_hand(joints, (B, 21, 3), 'joints'), per_hand(joints_conf, (B, 21), 'joints_conf')
+    tu, cu, po = per_hand(joint_uv, (B, 21, 2), 'joint_uv'), per_hand(uv_conf, (B, 21), 'uv_conf'), per_hand(para_out, (B, 64), 'para_out')
+    opts = _capi.ManoFitStartOpts(float(w_verts), float(w_joints), int(bool(root)), int(bool(cam)), int(bool(search)))
+    res, hs = [], []
+    P = _capi.ptr
+    for h in range(hands):
+        r = {'para': po[h] if po[h] is not None else torch.empty(B, 64, device=dev), 'status': torch.empty(B, dtype=torch.int32, device=dev),
+             'choice': torch.empty(B, dtype=torch.int32, device=dev), 'info': torch.empty(B, 4, device=dev)}
+        hs.append(_capi.ManoFitStartHand(init[h].data_ptr(), r['para'].data_ptr(), P(tv[h]), P(tj[h]), P(cj[h]), P(tu[h]), P(cu[h]), r['status'].data_ptr(),
+                                         r['choice'].data_ptr(), r['info'].data_ptr()))
+        res.append(r)
+    with torch.cuda.device(dev):
+        _capi.check(_capi.lib().dir_mano_fit_start((_capi.ManoTables * hands)(*tables_lr), (_capi.ManoFitStartHand * hands)(*hs), C.byref(opts), hands, B,
+                                                   _capi.stream_ptr()), 'dir_mano_fit_start')
+    return res

@@ -8,6 +8,14 @@ written out in include/dir_hip.h ("MANO fitting"); nothing here does arithmetic 
 `layer_or_tables`: a dir_amd.manopth.manolayer.ManoLayer (its own center_idx), a _capi.ManoTables, or a list of two of either for a pair of
 hands; with a pair every other tensor argument is a list of two (an entry may be None).  The defaults (lr, weights, iteration counts) are NOT
 tuned on real MANO tables or real keypoints.
+
+    st = start_mano(layer, neutral_para(B), verts=meshes)         # dir_mano_fit_start: root and camera in closed form, one launch
+    st.para [B,64], st.status [B], st.choice [B], st.info [B,4]
+    res = fit_mano(layer, neutral_para(B), verts=meshes, start='closed')      # the two launches, the fit anchored at the started parameters
+
+The start (include/dir_hip.h, "MANO fitting: closed-form start") turns the root onto 3-D targets by a rigid alignment of the points that are
+rigid under it, or, with 2-D targets alone, picks one of the cube's 24 rotations, and fits the camera by least squares: an arbitrary rotation
+is no longer out of Adam's reach, and cam_scale need not be guessed.
 """
 import collections
 
@@ -19,8 +27,10 @@ from .. import functional as F
 GROUPS = F.MANO_FIT_GROUPS                                   # root 0:6, pca 6:51, betas 51:61, cam 61:64
 DEFAULT_WEIGHTS = {'w_verts': 1e4, 'w_joints': 1e4, 'w_uv': 1.0, 'w_pca': 0.0, 'w_beta': 0.0, 'w_init': 0.0}
 STATUS_REFLECTION, STATUS_PASSED_THROUGH, STATUS_NONFINITE_STEP = 1, 2, 4
+STATUS_ROOT_KEPT, STATUS_CAM_KEPT = 8, 16                    # start_mano only: a step that ran left p0's root / camera in place
 
 FitResult = collections.namedtuple('FitResult', 'para verts joints joint_uv mse_before mse_after status state')
+StartResult = collections.namedtuple('StartResult', 'para status choice info')
 
 
 def neutral_para(B, cam_scale=1.0, device='cuda'):
@@ -49,14 +59,52 @@ def _tables(x):
     return x if isinstance(x, _capi.ManoTables) else x.c_tables(x.center_idx)
 
 
+def _term_weights(weights, verts, joints, joint_uv):
+    if weights is None:
+        return {k: (DEFAULT_WEIGHTS[k] if t is not None else 0.0) for k, t in (('w_verts', verts), ('w_joints', joints), ('w_uv', joint_uv))}
+    return weights
+
+
+def start_mano(layer_or_tables, init, verts=None, joints=None, joints_conf=None, joint_uv=None, uv_conf=None, weights=None, root=True, cam=True, search=True):
+    """One launch of dir_mano_fit_start: init [B,64] (not written) with its root and camera moved in closed form towards the targets (fit_mano's, each
+    optional).  weights: fit_mano's dict (only w_verts and w_joints are read, as the two 3-D terms' weights against one another).  root / cam: the
+    step may write that group; search: with 2-D targets alone, try the cube's 24 rotations.  -> StartResult(para [B,64], status [B] (bit 0 reflection,
+    bit 1 non-finite input: both passed through; 8 root kept, 16 camera kept), choice [B] (the rotation the search wrote, else -1), info [B,4] (3-D
+    energy before, after; 2-D residual before, after)); lists of two per field for a pair."""
+    pair = isinstance(layer_or_tables, (list, tuple))
+    hands = 2 if pair else 1
+    ls = lambda x: list(x) if pair else [x]  # noqa: E731
+    opt = lambda x: None if x is None else [None if t is None else _capi.f32c(t) for t in ls(x)]  # noqa: E731
+    tabs = [_tables(x) for x in ls(layer_or_tables)]
+    p0 = [_capi.f32c(t) for t in ls(init)]
+    if len(tabs) != hands or len(p0) != hands:
+        raise ValueError('start_mano: a pair takes lists of two')
+    B, dev = p0[0].shape[0], p0[0].device
+    w = _term_weights(weights, verts, joints, joint_uv)
+    if B == 0:
+        rs = [StartResult(p.clone(), torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, 4, device=dev))
+              for p in p0]
+    else:
+        res = F.mano_fit_start(tabs, p0, opt(verts), opt(joints), opt(joints_conf), opt(joint_uv), opt(uv_conf), w.get('w_verts', 0.0), w.get('w_joints', 0.0),
+                               root, cam, search)
+        rs = [StartResult(r['para'], r['status'], r['choice'], r['info']) for r in res]
+    return StartResult(*[list(f) for f in zip(*rs)]) if pair else rs[0]
+
+
 def fit_mano(layer_or_tables, init, verts=None, joints=None, joints_conf=None, joint_uv=None, uv_conf=None, iters=200, lr=0.1, weights=None,
-             state=None, outputs=True, anchor=None, betas=(0.9, 0.999), eps=1e-8):
+             state=None, outputs=True, anchor=None, betas=(0.9, 0.999), eps=1e-8, start=None):
     """One launch of dir_mano_fit.  init [B,64] float32 on the GPU (not written); targets verts [B,778,3], joints [B,21,3] with joints_conf [B,21],
     joint_uv [B,21,2] with uv_conf [B,21] (each optional; a confidence of 0 selects the entry out, which may then hold NaN).  lr: a float, or a
     dict per group of GROUPS (a missing group is frozen).  weights: dict over w_verts, w_joints, w_uv, w_pca, w_beta, w_init; None: DEFAULT_WEIGHTS
     for the terms whose targets are given.  state: True for a fresh Adam state, or the `state` of an earlier result to go on from it (updated
     in place; pass the same `anchor` -- None: init -- so that a + b iterations equal the two runs bit for bit).  outputs=False: no verts /
-    joints / joint_uv.  -> FitResult (lists of two per field for a pair)."""
+    joints / joint_uv.  start: None (every launch and byte as without it), or 'closed': start_mano(init, the same targets and weights) runs first and
+    the fit starts from its parameters, which are also the anchor where none is given.  -> FitResult (lists of two per field for a pair)."""
+    if start not in (None, 'closed'):
+        raise ValueError("fit_mano: start is None or 'closed', got %r" % (start,))
+    if start == 'closed':
+        init = start_mano(layer_or_tables, init, verts, joints, joints_conf, joint_uv, uv_conf, weights).para
+        anchor = init if anchor is None else anchor
     pair = isinstance(layer_or_tables, (list, tuple))
     hands = 2 if pair else 1
     ls = lambda x: list(x) if pair else [x]  # noqa: E731
@@ -66,8 +114,7 @@ def fit_mano(layer_or_tables, init, verts=None, joints=None, joints_conf=None, j
     if len(tabs) != hands or len(p0) != hands:
         raise ValueError('fit_mano: a pair takes lists of two')
     B, dev = p0[0].shape[0], p0[0].device
-    if weights is None:
-        weights = {k: (DEFAULT_WEIGHTS[k] if t is not None else 0.0) for k, t in (('w_verts', verts), ('w_joints', joints), ('w_uv', joint_uv))}
+    weights = _term_weights(weights, verts, joints, joint_uv)
     if state is True:
         state = [new_state(B, dev) for _ in range(hands)]
         state = state if pair else state[0]

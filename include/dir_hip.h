@@ -29,7 +29,7 @@ extern "C" {
 #define DIR_E_LAUNCH (-2)   /* hipLaunchKernel / HIP runtime error          */
 #define DIR_E_NODEVICE (-3) /* no gfx950 device visible                     */
 
-#define DIR_ABI_VERSION 53
+#define DIR_ABI_VERSION 54
 
 int dir_abi_version(void);
 const char* dir_last_error(void);
@@ -187,6 +187,69 @@ typedef struct dir_mano_fit_opts {
 /* tables_host / hands_host: HOST arrays of `hands` (1 or 2) entries; grid = B x hands.  Enqueued on `stream`, graph-capture safe. */
 int dir_mano_fit(const dir_mano_tables* tables_host, const dir_mano_fit_hand* hands_host, const dir_mano_fit_opts* opts_host,
                  int hands, int B, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * MANO fitting: closed-form start (ABI 54; csrc/mano_fit_start.hip; nothing in the reference).  Adam takes lr-sized steps, so a fit that starts
+ * at the identity root spends its iterations turning the wrist and never reaches a far rotation.  dir_mano_fit_start moves p0's ROOT (6 floats)
+ * and CAMERA (3 floats) to where a closed form puts them and copies the other 55 floats; dir_mano_fit then starts from p_out.  One launch, one
+ * 256-thread workgroup per (sample, hand), ONE forward at p0 (the forward phases of csrc/mano_device.h), everything after it closed form.  fp32
+ * throughout, every sum in a fixed order, no atomics, no workspace, no host read, graph-capture safe; a row gives the same bits in any slot of
+ * any batch and in either hand slot.  tests/helpers/mano_start_ref.py restates the rule in torch.
+ *
+ * Per row.  R0 = the robust-6D rotation of p0[0:6]; V [778,3], J [21,3] = dir_mano_forward's verts and joints at p0 (centred as the tables say).
+ *   0. Pass-through.  p0 non-finite, or a target in use non-finite (dir_mano_fit's status bit 1, the same definition: a term is in use when its
+ *      pointer is given, an entry when its confidence is > 0): p_out = p0 bit for bit, status bit 1, choice -1, info 0.  R0 a reflection: the same
+ *      with status bit 0.
+ *   1. Pivot.  pi = 0 when center_idx >= 0, else the rest-pose chain joint 0 at p0's betas (j_template + j_shapedirs beta, row 0).  Multiplying
+ *      the root from the left by a rotation Q maps every output X to Q (X - pi) + pi (to ~1e-9 m: a float32 skinning row does not sum to 1).
+ *   2. Root from 3-D targets -- when verts_t or joints_t is given and opts.root != 0.  Over the points that are rigid under the root:
+ *        joints    RS = {0, 1, 5, 9, 13, 17} (wrist, thumb base, the four MCPs; pd_joint_xyz_* order), without joint 0 when root_palm; weight
+ *                  w_j = k_j c_j for c_j > 0 (c_j <= 0: selected out, never multiplied, may hold NaN), k_j = w_joints / 21;
+ *        vertices  all 778, weight w_v = k_v * weights[v][0] (the root's skinning weight), k_v = w_verts / 778;
+ *      k_j, k_v formed in double on the host and rounded once.  With x the model point and y its target:
+ *        S[a][b] = sum w (x - pi)_a (y - pi)_b      e0 = sum w |x - y|^2      W = sum w
+ *      each as (the joints of RS in index order, from 0) + (the vertices: lane t adds v = t, t + 256, ... in order, then the DPP tree of each
+ *      64-lane wave, then the four waves in order).  Q = the Horn rotation of S (csrc/horn_rotation.h, the one dir_procrustes_align runs);
+ *      e1 = sum w |Q (x - pi) + pi - y|^2 in the same order.  If W is not > 0, or S is all zero, or e1 is not <= e0: the root keeps p0's six
+ *      bits and status bit 3 (value 8) is set.  Otherwise R1 = Q R0 and p_out[0:6] = columns 0 and 1 of R1.
+ *      (Centring at a finger joint biases this, because the pivot then moves with the pose: accepted, it is a start.)
+ *   3. Root from 2-D targets only -- when neither verts_t nor joints_t is given, uv_t is given and opts.root, opts.cam and opts.search are all
+ *      != 0 (a candidate is scored under its own camera, so both groups are written or neither).  The candidates are the 24 proper rotations of
+ *      the cube: permutations `perm` of (0, 1, 2) in lexicographic order, within each the sign triples sg in the order (+,+,+), (+,+,-), (+,-,+),
+ *      ...; row r of P has sg[r] at column perm[r]; the ones with det +1 are kept and numbered k = 0 .. 23 in that order (k = 0 is the identity).
+ *      Candidate joints are P_k (J - pi) + pi; each candidate gets the camera of step 4 on them and e_k = its 2-D residual.  A candidate whose
+ *      denominator is not > 0, whose s is not finite and > 0 or whose e_k is not finite is dropped (s <= 0 is the mirrored camera).  The
+ *      smallest e_k wins, ties to the lowest k.  If nothing survives, or the best e_k is not <= the residual of p0's own root and camera, root and camera keep p0's bits, status
+ *      bits 3 and 4 are set and choice = -1.  Otherwise R1 = P_k R0, p_out[0:6] = its columns 0 and 1, the camera is the candidate's, choice = k.
+ *   4. Camera -- when uv_t is given and opts.cam != 0 (and step 3 did not run).  X_j = the xy of the joints under the root of step 2 (J itself
+ *      where that step did not run or kept p0's root, else Q (J - pi) + pi), over the keypoints with d_j > 0 in index order:
+ *        D = sum d    Xm = sum d X / D    Um = sum d U / D    s = sum d (X - Xm).(U - Um) / sum d |X - Xm|^2    t = Um - s Xm
+ *      (dir_mano_forward's uv = s xy + t).  Accepted only if the denominator is > 0, s is finite and > 0 and its residual sum d |s X + t - U|^2
+ *      is finite and <= the residual of p0's camera on the same X; otherwise p0's three bits stay and status bit 4 (value 16) is set.
+ *   5. The 45 PCA coefficients and the 10 betas are copied bit for bit, and so is every group whose switch is off.  p_out may alias p0.
+ * status (int32 per row, optional): bit 0 and bit 1 as above (step 0), bit 3 the root was not moved by a step that ran, bit 4 the camera was not.
+ * choice (int32 per row, optional): the candidate step 3 wrote, -1 otherwise.
+ * info [B,4] (optional): the weighted 3-D energy e0, then e1 (e0 again where the root was kept; 0, 0 where step 2 did not run); then the 2-D
+ *   residual sum d |s X + t - U|^2 at p0's root and camera, then at p_out's (0, 0 without uv_t). */
+typedef struct dir_mano_fit_start_hand {
+    const float* p0;          /* [B,64] start                                             */
+    float* p_out;             /* [B,64] (may alias p0)                                     */
+    const float* verts_t;     /* V* [B,778,3] or NULL                                      */
+    const float* joints_t;    /* J* [B,21,3] or NULL                                       */
+    const float* joints_conf; /* c  [B,21] or NULL (= 1)                                   */
+    const float* uv_t;        /* U* [B,21,2] or NULL                                       */
+    const float* uv_conf;     /* d  [B,21] or NULL (= 1)                                   */
+    int32_t* status;          /* [B] or NULL                                               */
+    int32_t* choice;          /* [B] or NULL                                               */
+    float* info;              /* [B,4] or NULL                                             */
+} dir_mano_fit_start_hand;
+typedef struct dir_mano_fit_start_opts {
+    float w_verts, w_joints;  /* the weights of the two 3-D terms against one another       */
+    int32_t root, cam, search;/* switches: != 0 = the step may write its group              */
+} dir_mano_fit_start_opts;
+/* tables_host / hands_host: HOST arrays of `hands` (1 or 2) entries; grid = B x hands.  Enqueued on `stream`. */
+int dir_mano_fit_start(const dir_mano_tables* tables_host, const dir_mano_fit_start_hand* hands_host, const dir_mano_fit_start_opts* opts_host,
+                       int hands, int B, void* stream);
 
 /* Backward of RegressorOffset's three Linears (models/dir.py:339-351).  w_left / w_right [64][1408], w_offset [3][2691]: the
  * nn.Linear weights in their own layout; tok [B,42,64] = the STE head output (tokens 0..20 left); prev_* the previous stage's
