@@ -76,6 +76,11 @@ class ResChainParams(C.Structure):       # dir_res_chain_params
         (n, C.c_int32) for n in ('Cin', 'Cmid', 'Cout', 'dtype')]
 
 
+class BneckBlockParams(C.Structure):     # dir_bneck_block_params
+    _fields_ = [(n, C.c_void_p) for n in ('wstream', 'scale2', 'shift2', 'scale3', 'shift3', 'scale1n', 'shift1n')] + [
+        (n, C.c_int32) for n in ('planes', 'n_next', 'dtype')]
+
+
 class GemmDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ('M', 'N', 'K', 'lda', 'ldb', 'ldc', 'trans_a', 'trans_b', 'accumulate', 'batch')] + \
                [(n, C.c_int64) for n in ('stride_a', 'stride_b', 'stride_c')]
@@ -181,7 +186,7 @@ class RenderLights(C.Structure):         # dir_render_lights
                 ('shininess', C.c_float)]
 
 
-ABI_VERSION = 54         # DIR_ABI_VERSION (include/dir_hip.h)
+ABI_VERSION = 55         # DIR_ABI_VERSION (include/dir_hip.h)
 DT_F32, DT_BF16, DT_F16X3, DT_F16X1, DT_F16X3P, DT_F16X1P, DT_F16 = 0, 1, 3, 4, 5, 6, 7      # DT_F16: f16 STORAGE (round 5)
 CONV_RELU, CONV_PRE_RELU = 1, 2
 
@@ -227,6 +232,8 @@ _SIGNATURES = {
     'dir_bottleneck_tail_forward': (C.c_int, [C.POINTER(BneckTailParams), _p, _p, _p, _p, C.c_longlong, _p]),
     'dir_residual_chain_supported': (C.c_int, [_i] * 11),
     'dir_residual_chain_forward': (C.c_int, [C.POINTER(ResChainParams), _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
+    'dir_bottleneck_block_supported': (C.c_int, [_i] * 6),
+    'dir_bottleneck_block_forward': (C.c_int, [C.POINTER(BneckBlockParams), _p, _p, _p, _p, _i, _i, _i, _p]),
     'dir_stem_pool_forward': (C.c_int, [_p, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _p, _p, _p, _p, _i, _i, _i, _p]),
     'dir_stem_pool_forward_dt': (C.c_int, [_p, _i, _i, C.POINTER(C.c_float), C.POINTER(C.c_float), _p, _p, _p, _p, _i, _i, _i, _p]),
     'dir_maxpool3x3s2': (C.c_int, [_p, _p, _i, _i, _i, _i, _i, _p]),
@@ -348,7 +355,7 @@ _SIGNATURES = {
 #    + whatever the caller announced for this call with annotate(): 'flops', 'bytes' (algorithmic work), 'shape', 'op'}
 PROFILE = None
 _pending = {}
-_NO_PROFILE = ('dir_conv2d_as_supported', 'dir_conv2d_as_chain_supported', 'dir_residual_chain_supported', 'dir_abi_version', 'dir_last_error', 'dir_device_info', 'dir_launch_log_reset', 'dir_launch_log_get', 'dir_launch_log_note',
+_NO_PROFILE = ('dir_conv2d_as_supported', 'dir_conv2d_as_chain_supported', 'dir_residual_chain_supported', 'dir_bottleneck_block_supported', 'dir_abi_version', 'dir_last_error', 'dir_device_info', 'dir_launch_log_reset', 'dir_launch_log_get', 'dir_launch_log_note',
                'dir_bone_fusion_scratch_bytes', 'dir_dense_losses_workspace_bytes', 'dir_dense_losses_backward_workspace_bytes',
                'dir_gemm_f32_splitk_workspace_bytes', 'dir_bn_train_workspace_bytes', 'dir_bn_sync_workspace_bytes', 'dir_bn_frozen_workspace_bytes', 'dir_jpeg_planes_bytes', 'dir_render_workspace_bytes', 'dir_render_adjacency_bytes', 'dir_render_shaded_workspace_bytes', 'dir_colsum_workspace_bytes', 'dir_conv2d_wgrad_workspace_bytes', 'dir_conv2d_wgrad_f16x3_workspace_bytes',
                'dir_one_euro_state_bytes', 'dir_mano_para_smooth_state_bytes', 'dir_grad_norm_workspace_bytes')

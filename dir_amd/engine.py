@@ -19,7 +19,7 @@ import torch
 
 from . import _capi
 from ._capi import CONV_PRE_RELU, CONV_RELU, DT_BF16, DT_F16, DT_F16X1, DT_F16X1P, DT_F16X3, DT_F16X3P, DT_F32, ConvDesc
-from .packing import pack_as_weights, pack_stream_weights, pack_tail_stream      # noqa: F401  (re-exported: tests and tools take them from here)
+from .packing import pack_as_weights, pack_l3_stream, pack_stream_weights, pack_tail_stream      # noqa: F401  (re-exported: tests and tools take them from here)
 
 F32 = torch.float32
 IMAGENET_MEAN = (C.c_float * 3)(0.485, 0.456, 0.406)      # apps/eval.py:49-50
@@ -469,6 +469,55 @@ class BneckTailOp(object):
         return out, y1n
 
 
+class BneckBlockOp(object):
+    """dir_bottleneck_block_forward: conv2 + bn2 + ReLU + conv3 + bn3 + identity + ReLU of a layer3 identity bottleneck and, where c1n is
+    given, the next block's conv1 + bn1 + ReLU in one launch (models/backbone/resnet.py:126-140,122-124): y2 stays on the CU.  Bit-identical
+    to c2 followed by BneckTailOp (c1n given) or by c3 with the residual (c1n None).  For the tuning tables the launch stays the layers it
+    replaces: its profile record carries op = c2 and covers = (`covered`,) -- the BneckTailOp or c3 that runs with DIR_L3_CHAIN=0."""
+
+    def __init__(self, c2, c3, c1n=None, covered=None):
+        self.c2, self.c3, self.c1n = c2, c3, c1n
+        self.covers = (covered if covered is not None else c3,)
+        self.cout, self.cin, self.kh, self.kw, self.stride = c3.cout, c2.cin, 3, 3, 1
+        self.variant = c2.variant                              # (the 3x3's row; a single kernel: every variant code is a no-op)
+        # the stream is packed here, eagerly: nothing is allocated or copied on the first call, which may be under graph capture
+        self.stream = pack_l3_stream(c2.w, c3.w.reshape(c3.cout, c3.cin), None if c1n is None else c1n.w.reshape(c1n.cout, c1n.cin), dtype=c2.dtype)
+        n = (lambda t: None) if c1n is None else _capi.ptr        # noqa: E731
+        self.params = _capi.BneckBlockParams(_capi.ptr(self.stream), _capi.ptr(c2.scale), _capi.ptr(c2.shift), _capi.ptr(c3.scale), _capi.ptr(c3.shift),
+                                             n(c1n.scale if c1n is not None else None), n(c1n.shift if c1n is not None else None),
+                                             c2.cout, c1n.cout if c1n is not None else 0, _dt(c2.dtype))
+
+    @staticmethod
+    def applies(c2, c3, c1n, dtype):
+        ok = (dtype in HALF and c2.arith is None and (c2.kh, c2.kw, c2.stride, c2.pad, c2.cin, c2.cout) == (3, 3, 1, 1, 256, 256)
+              and c2.scale is not None and c2.pre_scale is None and (c2.flags & CONV_RELU)
+              and (c3.kh, c3.stride, c3.cin, c3.cout) == (1, 1, 256, 1024) and c3.scale is not None and c3.pre_scale is None and (c3.flags & CONV_RELU))
+        return bool(ok and (c1n is None or ((c1n.kh, c1n.stride, c1n.cin, c1n.cout) == (1, 1, 1024, 256) and c1n.scale is not None
+                                            and c1n.pre_scale is None and (c1n.flags & CONV_RELU))))
+
+    def supported(self, y1, x):
+        B, H, W, Pn = y1.shape
+        return bool(y1.dtype == self.c2.dtype and x.dtype == y1.dtype and y1.is_contiguous() and x.is_contiguous() and Pn == 256
+                    and tuple(x.shape) == (B, H, W, 1024)
+                    and _capi.lib().dir_bottleneck_block_supported(_dt(y1.dtype), 256, self.params.n_next, B, H, W))
+
+    def __call__(self, y1, x):
+        """y1: this block's conv1 output [B,H,16,256]; x: the block input [B,H,16,1024] (identity residual) -> (block output, next y1 | None)"""
+        B, H, W, _ = y1.shape
+        if _TLS.capture_fused is not None:
+            _TLS.capture_fused.append((self, (y1, x), {}))
+        out = torch.empty(B, H, W, 1024, device=y1.device, dtype=y1.dtype)
+        y1n = torch.empty(B, H, W, 256, device=y1.device, dtype=y1.dtype) if self.c1n is not None else None
+        if _capi.PROFILE is not None:
+            m, n2 = B * H * W, self.params.n_next
+            _capi.annotate(family='conv', flops=2.0 * m * (256 * 9 * 256 + 256 * 1024 + 1024 * n2), op=self.c2, covers=self.covers, dtype='bf16',
+                           shape='M=%d block 3x3(256)+1x1(->1024)+res%s' % (m, '+1x1(->%d)' % n2 if n2 else ''),
+                           bytes=(m * (256 + 2 * 1024 + n2) + 256 * 9 * 256 + 1024 * 256 + n2 * 1024) * 2)
+        _capi.check(_capi.lib().dir_bottleneck_block_forward(C.byref(self.params), _capi.ptr(y1), _capi.ptr(x), _capi.ptr(out), _capi.ptr(y1n), B, H, W,
+                                                             _capi.stream_ptr()), 'dir_bottleneck_block_forward')
+        return out, y1n
+
+
 def stem_conv_op(w, scale, shift, dtype):
     """7x7/2 stem over 2x2 space-to-depth blocks (dir_stem_prep_s2d): a 4x4 stride-1 convolution whose K-slab is a block-row
     window of 4 blocks x 16 channels; w'[n][j*16 + (dy*2+dx)*4 + c][r] = w[n, c, 2r+dy-1, 2j+dx-1]   (w = conv1.weight [64,3,7,7])"""
@@ -498,6 +547,7 @@ class BackboneOp(object):
     fused_stem = os.environ.get('DIR_FUSED_STEM', '1') != '0'       # bf16 mode: conv1 + bn1 + ReLU + maxpool in one launch
     bneck_chain = os.environ.get('DIR_BNECK_CHAIN', '1') != '0'     # bf16 mode, layer1: conv2 + conv3 (+ next conv1) in one launch
     bneck_tail = os.environ.get('DIR_BNECK_TAIL', '1') != '0'       # bf16 mode, layer2 / layer3: conv3 + residual + next conv1 in one launch
+    l3_chain = os.environ.get('DIR_L3_CHAIN', '1') != '0'           # 16-bit storage, layer3 identity blocks: conv2 + conv3 (+ next conv1) in one launch
 
     def __init__(self, sd, p, dtype, device):
         dt = self.dtype = dtype
@@ -552,6 +602,16 @@ class BackboneOp(object):
                     if BneckTailOp.applies(blk['c3'], nxt, dt):
                         blk['tail'] = BneckTailOp(blk['c3'], nxt)
 
+        # layer3's identity blocks from conv2 on as ONE launch each (dir_bottleneck_block_forward): the next conv1 rides along where the tail
+        # launch it replaces had it (same k-slots), the layer's last block ends at its output
+        if self.l3_chain:
+            for i, blk in enumerate(self.layers[2]):
+                if 'dual' in blk or 'chain' in blk:
+                    continue
+                nxt = blk['tail'].c1n if 'tail' in blk else None
+                if BneckBlockOp.applies(blk['c2'], blk['c3'], nxt, dt):
+                    blk['block'] = BneckBlockOp(blk['c2'], blk['c3'], nxt, covered=blk.get('tail'))
+
     def __call__(self, img):
         L, dt, dev = _capi.lib(), self.dtype, self.device
         B = img.shape[0]
@@ -597,6 +657,11 @@ class BackboneOp(object):
                     x, y1 = blk['chain'](y1 if y1 is not None else blk['c1'](x), x, decimate=dec)
                     x_dec = dec
                     continue
+                if 'block' in blk and self.l3_chain:
+                    y1 = y1 if y1 is not None else blk['c1'](x)
+                    if blk['block'].supported(y1, x):
+                        x, y1 = blk['block'](y1, x)
+                        continue
                 if 'tail' in blk and (x.shape[0] * x.shape[1] * x.shape[2]) % 64 == 0:
                     x, y1 = blk['tail'](blk['c2'](y1 if y1 is not None else blk['c1'](x)), x)
                 elif 'dual' in blk:                                  # conv3 + projection shortcut in one launch

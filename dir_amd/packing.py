@@ -30,6 +30,22 @@ def pack_stream_weights(w_nk, dtype=torch.bfloat16):
     return pack_as_weights(w_nk.detach().to(dtype).reshape(N, 1, 1, K), 2 if N % 256 == 0 else 1)
 
 
+def pack_l3_stream(w2_ohwi, w3, w1n=None, dtype=torch.bfloat16):
+    """dir_bottleneck_block_forward's weight stream (include/dir_hip.h) from conv2.weight [256][3][3][256] (NHWC-ordered, as ConvOp keeps it),
+    conv3.weight [1024, 256] and the next conv1.weight [256, 1024] (or None): per wave its 144 conv2 fragments (pack_as_weights with one block
+    per wave), then per 512-channel half its conv3 and conv1 fragments -- pack_tail_stream's where the next conv1 is fused, a convolution's
+    k-slots for conv3 where it is not (the launch replaced is then a convolution).  [8 waves][144 + 2 (32 + NCF)][64 lanes][8]."""
+    w2 = w2_ohwi.detach().to(dtype)
+    w3 = w3.detach().reshape(w3.shape[0], -1).to(dtype)
+    assert tuple(w2.shape) == (256, 3, 3, 256) and tuple(w3.shape) == (1024, 256)
+    a = pack_as_weights(w2, 1).reshape(8, 144, 64, 8)                              # [2 slices][4 waves] = channel block 32 w
+    if w1n is not None:
+        u = pack_tail_stream(w3, w1n, 8, dtype=dtype).to(w2.device).reshape(2, 8, 64, 64, 8)
+    else:                                                                          # [32 channel blocks = (half, wave, cb)][4 slabs][4 k-steps]
+        u = pack_as_weights(w3.reshape(1024, 1, 1, 256), 1).reshape(2, 8, 32, 64, 8)
+    return torch.cat([a, u[0], u[1]], 1).contiguous()
+
+
 def pack_tail_stream(w3, w1n, waves=8, dtype=torch.bfloat16):
     """dir_bottleneck_tail_forward's weight stream (include/dir_hip.h): conv3.weight [4P, P] and the next conv1.weight [N2, 4P]
     as bf16 MFMA A-operand fragments in the order the kernel's waves consume them, [4P/512][waves][NBF + NCF][64 lanes][8]

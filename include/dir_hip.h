@@ -29,7 +29,7 @@ extern "C" {
 #define DIR_E_LAUNCH (-2)   /* hipLaunchKernel / HIP runtime error          */
 #define DIR_E_NODEVICE (-3) /* no gfx950 device visible                     */
 
-#define DIR_ABI_VERSION 54
+#define DIR_ABI_VERSION 55
 
 int dir_abi_version(void);
 const char* dir_last_error(void);
@@ -1048,6 +1048,39 @@ int dir_residual_chain_supported(int dtype, int Cin, int Cmid, int Cout, int B, 
                                  int out_coff);
 int dir_residual_chain_forward(const dir_res_chain_params* p, const void* x, void* out, int B, int H, int W, int in_cstride, int in_coff,
                                int out_cstride, int out_coff, void* stream);
+
+/* a1, layer3 geometry (planes 256, block width 1024, 16-wide maps; ABI 55; csrc/l3_chain.hip): one identity bottleneck from conv2 on, and the
+ * 1x1 head of the next one, in ONE launch
+ *   models/backbone/resnet.py:126-130   y2 = relu(bn2(conv2(y1)))                          conv2: 3x3 / s1 / p1, 256 -> 256; y2 stays on the CU
+ *   models/backbone/resnet.py:132-140   out = relu(bn3(conv3(y2)) + identity)              conv3: 1x1, 256 -> 1024
+ *   models/backbone/resnet.py:122-124   y1_next = relu(bn1'(conv1'(out)))                  conv1': 1x1, 1024 -> n_next (n_next = 256; 0: none)
+ * 16-bit NHWC, contiguous: y1 [B,H,16,256], residual [B,H,16,1024] (the block input), out [B,H,16,1024], y1_next [B,H,16,256] (ignored when
+ * n_next = 0).  W = 16, H a multiple of 4: a workgroup owns four whole rows of one image.  out and y1_next are the only memory written.
+ * Bit-identical to dir_conv2d_as_forward (conv2) followed by dir_bottleneck_tail_forward (n_next = 256) or by conv3 as dir_conv2d_forward with
+ * the residual (n_next = 0): same fp32 chains, same rounding points (y2, out and y1_next rounded to the storage kind).
+ * wstream: the three weight matrices as MFMA A-operand fragments (16 bytes per lane, 1 KB per fragment) in the order the kernel's 8 waves consume
+ * them, [8 waves][144 + 2 (32 + NCF) fragments][64 lanes][8], NCF = 32 (n_next = 256) | 0; for wave w, lane l:
+ *   conv2 fragment f < 144          step = f / 4 = (64-channel slab) * 9 + tap, ks = f % 4 (dir_conv2d_as_forward's stream with one block per wave):
+ *                                   w2[32 w + (l & 31)][tap][64 slab + 8 ks + 32 (l >> 5) .. + 8]
+ *   then per 512-channel half: 32 conv3 fragments (channel block cb = f / 16, k-step ks = f % 16) and NCF conv1' fragments fc
+ *     n_next = 256                  w3[half 512 + 64 w + 32 cb + (l & 31)][16 ks + 8 (l >> 5) .. + 8]        (dir_bottleneck_tail_forward's stream)
+ *                                   w1n[32 w + (l & 31)][half 512 + 16 fc + 8 (l >> 5) .. + 8]
+ *     n_next = 0                    w3[half 512 + 64 w + 32 cb + (l & 31)][64 (ks / 4) + 8 (ks % 4) + 32 (l >> 5) .. + 8]   (a convolution's k-slots)
+ * (dir_amd/packing.py::pack_l3_stream builds it).  scale / shift: the folded eval-mode BatchNorms, fp32 device pointers.
+ * dir_bottleneck_block_supported: 1 if the forward call takes these shapes, else 0 (the caller then runs the two launches); no launch.
+ * dir_bottleneck_block_forward returns DIR_E_INVALID for anything dir_bottleneck_block_supported rejects, before any launch. */
+typedef struct dir_bneck_block_params {
+    const void* wstream;
+    const float* scale2; const float* shift2;      /* [256]  */
+    const float* scale3; const float* shift3;      /* [1024] */
+    const float* scale1n; const float* shift1n;    /* [n_next], or NULL with n_next = 0 */
+    int32_t planes;   /* 256 */
+    int32_t n_next;   /* 256 | 0 */
+    int32_t dtype;    /* DIR_DT_BF16 | DIR_DT_F16: storage kind of the tensors and of the weight stream */
+} dir_bneck_block_params;
+int dir_bottleneck_block_supported(int dtype, int planes, int n_next, int B, int H, int W);
+int dir_bottleneck_block_forward(const dir_bneck_block_params* p, const void* y1, const void* residual, void* out, void* y1_next,
+                                 int B, int H, int W, void* stream);
 
 /* a13 / 8f rank 2, forward half: the training objective, models/dir.py:542-594 (SmoothL1Loss models/loss.py:63-93, EdgeLengthLoss
  * :36-60, NormalVectorLoss :6-33, nn.CrossEntropyLoss(weight), lovasz_softmax models/lovasz_loss.py:155-202).  Forward values;
