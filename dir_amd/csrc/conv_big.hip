@@ -1,4 +1,4 @@
-// The 256 x 256 block tile (DIR_CONV_VARIANT 11): the lever DESIGN.md 7 names for the MFMA-bound layers whose grid still fills the chip at
+// The 256 x 256 block tile (DIR_CONV_VARIANT 11): the lever docs/rounds/DESIGN_rounds_1_to_5.md 7 names for the MFMA-bound layers whose grid still fills the chip at
 // this tile (at B = 64: conv_final and the merged seg / dense heads, 3x3 256 -> 256 at 32 x 32 -- 256 tiles).  Same maths, operand layout,
 // K order and fp32 accumulation order as conv.hip / conv_pipe.hip (outputs are bit-identical); what changes is the shape of the work:
 //

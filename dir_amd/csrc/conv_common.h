@@ -42,7 +42,7 @@ __device__ __forceinline__ void lds_dma16_m0(i32x4 rsrc, unsigned lds_addr, unsi
 }
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
-// NOTE (kept as a warning): hiding REGISTER-destination loads from the compiler (inline-asm buffer_load +
+// NOTE (kept as a warning, see docs/rounds/DESIGN_rounds_1_to_5.md 4): hiding REGISTER-destination loads from the compiler (inline-asm buffer_load +
 // hand-counted vmcnt) to deepen the register pipeline is UNSAFE -- hipcc may split / copy the live range of an asm-loaded VGPR
 // before the data has landed (intermittent garbage on full grids; tests/test_gpu_conv.py::
 // test_conv_full_size_chunk_consistency is the regression test).  The deep pipelines here use LDS-DMA (no VGPR destination).
@@ -64,7 +64,7 @@ __device__ __forceinline__ uint32_t relu2bf(uint32_t v) {
 
 // f16 STORAGE (DIR_DT_F16, round 5): feature maps and weights held as IEEE binary16 -- the bytes, addressing, LDS-DMA path and MFMA rate of
 // the bf16 mode with an 11-bit significand instead of 8: the rounding of every stored map is 8x finer (the bf16 mode's 0.036 / 0.050 mm at
-// the init stage is the accumulated rounding of the backbone's 53 stored maps).  The range is 65504: stores saturate (MODE.FP16_OVFL,
+// the init stage is the accumulated rounding of the backbone's 53 stored maps, docs/rounds/DESIGN_rounds_1_to_5.md 10).  The range is 65504: stores saturate (MODE.FP16_OVFL,
 // half_kernel_init) instead of producing inf.  A distinct tag type so that every kernel template instantiates twice; 2 bytes like bf16_t.
 struct f16s_t { unsigned short u; };
 typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;

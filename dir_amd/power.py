@@ -8,7 +8,7 @@ import subprocess
 import threading
 import time
 
-IDLE_W = 243.0       # package power of an idle MI355X as rocm-smi reports it on the boxes this was measured on; measured live when possible
+IDLE_W = 243.0       # package power of an idle MI355X as rocm-smi reports it on the boxes this was measured on (docs/rounds/DESIGN_rounds_1_to_5.md 9); measured live when possible
 
 
 def smi_sample():

@@ -1,4 +1,4 @@
-"""The decoder's last four convolutions as two chained launches (dir_amd/engine.py::ConvChainOp over conv_as.hip's chained mode): conv_final.0 ->
+"""The decoder's last four convolutions as two chained launches (dir_amd/engine/decoder.py::ConvChainOp over conv_as.hip's chained mode): conv_final.0 ->
 conv_final.3 (models/dir.py:474-476) and the merged seg | dense 3x3 -> their 1x1s (models/dir.py:425-433).  With DIR_HEAD_CHAIN off and on the
 whole forward -- every output, every tap -- is torch.equal, a captured graph replays the same bits, and the kernel table keeps ONE ROW PER LAYER:
 the same 52 rows in the same order either way, so the shipped table loads unchanged."""

@@ -1,5 +1,5 @@
 """GPU parity of the fused layer3 bottleneck block (l3_chain.hip, dir_bottleneck_block_forward) against the two launches it replaces
-(dir_amd/engine.py::BackboneOp._layers: blk['c2'], then BneckTailOp -- or, for the layer's last block, c3 with the residual;
+(dir_amd/engine/backbone.py::BackboneOp._layers: blk['c2'], then BneckTailOp -- or, for the layer's last block, c3 with the residual;
 models/backbone/resnet.py:126-140,122-124).  Those are themselves pinned against the oracle (test_gpu_conv_as.py, test_gpu_tail.py).  The
 kernel accumulates in their K order and k-slot assignment and rounds y2 / out / y1n at their points, so every comparison is torch.equal.
 Every fused call writes into buffers surrounded by sentinel values, which are checked afterwards: out and y1n are the only memory written."""

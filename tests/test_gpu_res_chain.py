@@ -1,5 +1,5 @@
 """GPU parity of the fused decoder Residual block (res_chain.hip, dir_residual_chain_forward) against the three launches it replaces
-(dir_amd/engine.py::ResidualOp: conv1 with the pre-activation -> conv2 3x3 -> conv3 + skip_layer as one GEMM; models/backbone/hourglass.py:33-70).
+(dir_amd/engine/decoder.py::ResidualOp: conv1 with the pre-activation -> conv2 3x3 -> conv3 + skip_layer as one GEMM; models/backbone/hourglass.py:33-70).
 The kernel accumulates in the same K order and k-slot assignment and rounds y1 / y2 / out at the same points, so every comparison here is
 torch.equal: op level (both storage kinds, both map sizes, B = 1 / 3 / 64, output into a channel slice), the image border, the whole forward,
 graph replay, the argument checks, and the row count of the shipped kernel table."""
