@@ -33,6 +33,13 @@ class ManoFitOpts(C.Structure):        # dir_mano_fit_opts
 
 
 MANO_FIT_STATE = 132     # DIR_MANO_FIT_STATE
+MANO_FIT_SEQ_STATE = 24  # DIR_MANO_FIT_SEQ_STATE
+MANO_FIT_SEQ_LANES = 256 # DIR_MANO_FIT_SEQ_LANES
+
+
+class ManoFitSeqOpts(C.Structure):     # dir_mano_fit_seq_opts
+    _fields_ = [(n, C.c_float) for n in ('w_t_root', 'w_t_pca', 'w_t_cam')] + [('share_betas', C.c_int32), ('seq_start_host', C.POINTER(C.c_int32)),
+                                                                               ('seq_state', C.c_void_p * 2)]
 
 
 class ManoFitStartHand(C.Structure):   # dir_mano_fit_start_hand
@@ -186,7 +193,7 @@ class RenderLights(C.Structure):         # dir_render_lights
                 ('shininess', C.c_float)]
 
 
-ABI_VERSION = 55         # DIR_ABI_VERSION (include/dir_hip.h)
+ABI_VERSION = 56         # DIR_ABI_VERSION (include/dir_hip.h)
 DT_F32, DT_BF16, DT_F16X3, DT_F16X1, DT_F16X3P, DT_F16X1P, DT_F16 = 0, 1, 3, 4, 5, 6, 7      # DT_F16: f16 STORAGE (round 5)
 CONV_RELU, CONV_PRE_RELU = 1, 2
 
@@ -267,6 +274,9 @@ _SIGNATURES = {
     'dir_mano_backward_pair': (C.c_int, [C.POINTER(ManoTables), _p, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _i, _p, _i, _p, _i, _i, _i, _p]),
     'dir_mano_fit': (C.c_int, [C.POINTER(ManoTables), C.POINTER(ManoFitHand), C.POINTER(ManoFitOpts), _i, _i, _p]),
     'dir_mano_fit_start': (C.c_int, [C.POINTER(ManoTables), C.POINTER(ManoFitStartHand), C.POINTER(ManoFitStartOpts), _i, _i, _p]),
+    'dir_mano_fit_sequence_workspace_bytes': (C.c_size_t, [_i, _i, _i]),
+    'dir_mano_fit_sequence': (C.c_int, [C.POINTER(ManoTables), C.POINTER(ManoFitHand), C.POINTER(ManoFitOpts), C.POINTER(ManoFitSeqOpts), _p, _i, _i, _i, _p,
+                                        _p, C.c_size_t, _p]),
     'dir_regress_backward': (C.c_int, [_p] * 17 + [_i, _p]),
     'dir_gemm_f32': (C.c_int, [C.POINTER(GemmDesc), _p, _p, _p, _p, _p]),
     'dir_gemm_f32_grouped': (C.c_int, [C.POINTER(GemmDesc), C.POINTER(GemmGroups), _p, _p, _p, _p, _p]),
@@ -358,7 +368,7 @@ _pending = {}
 _NO_PROFILE = ('dir_conv2d_as_supported', 'dir_conv2d_as_chain_supported', 'dir_residual_chain_supported', 'dir_bottleneck_block_supported', 'dir_abi_version', 'dir_last_error', 'dir_device_info', 'dir_launch_log_reset', 'dir_launch_log_get', 'dir_launch_log_note',
                'dir_bone_fusion_scratch_bytes', 'dir_dense_losses_workspace_bytes', 'dir_dense_losses_backward_workspace_bytes',
                'dir_gemm_f32_splitk_workspace_bytes', 'dir_bn_train_workspace_bytes', 'dir_bn_sync_workspace_bytes', 'dir_bn_frozen_workspace_bytes', 'dir_jpeg_planes_bytes', 'dir_render_workspace_bytes', 'dir_render_adjacency_bytes', 'dir_render_shaded_workspace_bytes', 'dir_colsum_workspace_bytes', 'dir_conv2d_wgrad_workspace_bytes', 'dir_conv2d_wgrad_f16x3_workspace_bytes',
-               'dir_one_euro_state_bytes', 'dir_mano_para_smooth_state_bytes', 'dir_grad_norm_workspace_bytes')
+               'dir_one_euro_state_bytes', 'dir_mano_para_smooth_state_bytes', 'dir_grad_norm_workspace_bytes', 'dir_mano_fit_sequence_workspace_bytes')
 
 
 def annotate(**kw):

@@ -3,7 +3,7 @@
 
     python -m dir_amd.apps.fit_mano --model CKPT --targets T.npz --out O.npz [--iters 200] [--lr 0.1] [--lr_root --lr_pca --lr_betas --lr_cam]
                                     [--bs 256] [--center 0] [--cam_scale 1.0] [--w_verts 1e4 --w_joints 1e4 --w_uv 1 --w_pca 0 --w_beta 0
-                                    --w_init 0] [--ema] [--start neutral|closed]
+                                    --w_init 0] [--ema] [--start neutral|closed] [--sequences [--w_t_root 1 --w_t_pca 1 --w_t_cam 1] [--per_frame_shape]]
 
 The MANO tables come from the checkpoint (init_regressor.mano_layer_{left,right}.th_*), as in apps.predict.  T.npz holds, per side in
 (left, right), any of  verts_<side> [N,778,3],  joints_<side> [N,21,3] with joints_conf_<side> [N,21],  joint_uv_<side> [N,21,2] (the crop's
@@ -17,6 +17,14 @@ targets by a rigid alignment (with 2-D targets alone: the best of the cube's 24 
 (utils/mano_fit.py start_mano), so targets rotated anywhere are reached and --cam_scale need not be guessed; the fit is anchored at the started
 parameters, and O.npz gains start_<side> [N,64], start_status_<side> [N] (8: the root was kept, 16: the camera was kept) and start_choice_<side>
 [N] (the rotation the 2-D search wrote, else -1).  The defaults are NOT tuned on real MANO tables or real keypoints.
+
+--sequences: the N hands of a side are the frames of S sequences laid end to end, T.npz carries seq_len [S] (ints >= 1 summing to N; both sides share
+it), and ONE optimisation runs over each batch of whole sequences (dir_mano_fit_sequence, utils/mano_fit.py fit_mano_sequence): one shape per
+(sequence, side) unless --per_frame_shape, and the temporal term --w_t_root / --w_t_pca / --w_t_cam between neighbouring frames, which fills a frame
+whose confidences are all 0 from its neighbours.  A batch takes whole sequences up to --bs frames (a longer sequence is a batch of its own).  O.npz gains
+betas_<side> [S,10] (the sequence's shape: para_<side>'s 51:61 of its first frame that did not pass through; NaN where there is none) and
+seq_status_<side> [S] (2: no usable frame, 4: the shape was frozen); status_<side> gains bit 3 (a non-finite target in use: the frame's data terms were
+dropped).  Without --sequences every byte written is what it is without these flags.  The temporal defaults are NOT tuned on real tracks.
 """
 import time
 
@@ -62,9 +70,23 @@ def tables_from_checkpoint(state, center=0, device='cuda'):
     return {s: pack_mano(sd, 'init_regressor.mano_layer_' + s, s, None if center < 0 else center, keep) for s in SIDES}, keep
 
 
-def fit_targets(tables, targets, iters=200, lr=0.1, weights=None, bs=256, cam_scale=1.0, device='cuda', start='neutral'):
+def sequence_batches(seq_len, bs):
+    """whole sequences grouped into batches of at most bs frames (a longer sequence is a batch of its own) -> [(first sequence, one past the last)]"""
+    out, s0, n = [], 0, 0
+    for s, length in enumerate(seq_len):
+        if n and n + length > bs:
+            out.append((s0, s))
+            s0, n = s, 0
+        n += length
+    return out + [(s0, len(seq_len))] if len(seq_len) else out
+
+
+def fit_targets(tables, targets, iters=200, lr=0.1, weights=None, bs=256, cam_scale=1.0, device='cuda', start='neutral', seq_len=None, smooth=None,
+                share_betas=True):
     """targets: read_targets' dict -> {side: {para, verts, joints, joint_uv, mse_before, mse_after, status}} (numpy; with start='closed' also start,
-    start_status, start_choice).  Both sides with the same N go through one launch per batch as a pair, otherwise one side at a time."""
+    start_status, start_choice).  Both sides with the same N go through one launch per batch as a pair, otherwise one side at a time.
+    seq_len (ints [S] summing to every side's N): fit whole sequences (fit_mano_sequence with `smooth` and `share_betas`); the result gains betas [S,10]
+    and seq_status [S]."""
     import torch
 
     from ..utils import mano_fit as MF
@@ -75,9 +97,16 @@ def fit_targets(tables, targets, iters=200, lr=0.1, weights=None, bs=256, cam_sc
     for grp in groups:
         N = next(iter(targets[grp[0]].values())).shape[0]
         parts = {s: [] for s in grp}
-        for b0 in range(0, N, bs):
-            dev = lambda s, k: torch.from_numpy(np.ascontiguousarray(targets[s][k][b0:b0 + bs])).to(device) if k in targets[s] else None  # noqa: E731
-            n = min(bs, N - b0)
+        if seq_len is None:
+            spans = [(b0, min(b0 + bs, N), None) for b0 in range(0, N, bs)]
+        else:
+            if int(np.sum(seq_len)) != N or np.min(seq_len) < 1:
+                raise ValueError('fit_mano: seq_len must hold lengths >= 1 that sum to the %d hands of %s' % (N, grp[0]))
+            first = np.concatenate([[0], np.cumsum(seq_len)])
+            spans = [(int(first[a]), int(first[b]), [int(x) for x in seq_len[a:b]]) for a, b in sequence_batches(seq_len, bs)]
+        for b0, b1, lengths in spans:
+            dev = lambda s, k: torch.from_numpy(np.ascontiguousarray(targets[s][k][b0:b1])).to(device) if k in targets[s] else None  # noqa: E731
+            n = b1 - b0
             arg = lambda k: [dev(s, k) for s in grp] if len(grp) == 2 else dev(grp[0], k)  # noqa: E731
             init = [dev(s, 'init') if 'init' in targets[s] else MF.neutral_para(n, cam_scale, device) for s in grp]
             w = dict(weights or {})
@@ -91,13 +120,27 @@ def fit_targets(tables, targets, iters=200, lr=0.1, weights=None, bs=256, cam_sc
             if start == 'closed':
                 st = MF.start_mano(tabs, init, arg('verts'), arg('joints'), arg('joints_conf'), arg('joint_uv'), arg('uv_conf'), weights=w)
                 init = anchor = st.para
-            r = MF.fit_mano(tabs, init, arg('verts'), arg('joints'), arg('joints_conf'), arg('joint_uv'), arg('uv_conf'), iters=iters, lr=lr, weights=w, anchor=anchor)
+            if lengths is None:
+                r = MF.fit_mano(tabs, init, arg('verts'), arg('joints'), arg('joints_conf'), arg('joint_uv'), arg('uv_conf'), iters=iters, lr=lr, weights=w, anchor=anchor)
+            else:
+                r = MF.fit_mano_sequence(tabs, init, lengths, arg('verts'), arg('joints'), arg('joints_conf'), arg('joint_uv'), arg('uv_conf'), iters=iters, lr=lr,
+                                         weights=w, smooth=smooth, share_betas=share_betas, anchor=anchor)
             for h, s in enumerate(grp):
                 parts[s].append({k: (getattr(r, k)[h] if len(grp) == 2 else getattr(r, k)).cpu().numpy() for k in ('para', 'verts', 'joints', 'joint_uv', 'mse_before',
                                                                                                                     'mse_after', 'status')})
                 if st is not None:
                     parts[s][-1].update({n: (getattr(st, k)[h] if len(grp) == 2 else getattr(st, k)).cpu().numpy()
                                          for n, k in (('start', 'para'), ('start_status', 'status'), ('start_choice', 'choice'))})
+                if lengths is not None:
+                    d = parts[s][-1]
+                    d['seq_status'] = (r.seq_status[h] if len(grp) == 2 else r.seq_status).cpu().numpy()
+                    d['betas'] = np.full((len(lengths), 10), np.nan, np.float32)
+                    f0 = 0
+                    for i, length in enumerate(lengths):
+                        live = np.nonzero((d['status'][f0:f0 + length] & MF.STATUS_PASSED_THROUGH) == 0)[0]
+                        if live.size:
+                            d['betas'][i] = d['para'][f0 + live[0], 51:61]
+                        f0 += length
         for s in grp:
             out[s] = {k: np.concatenate([p[k] for p in parts[s]]) for k in parts[s][0]}
     return out
@@ -124,17 +167,30 @@ def main(argv=None):
     for k, d in (('w_verts', None), ('w_joints', None), ('w_uv', None), ('w_pca', 0.0), ('w_beta', 0.0), ('w_init', 0.0)):
         ap.add_argument('--' + k, type=float, default=d)
     ap.add_argument('--start', choices=('neutral', 'closed'), default='neutral', help='closed: root and camera of the start in closed form (dir_mano_fit_start)')
+    ap.add_argument('--sequences', action='store_true', help='the hands are frames of the sequences seq_len [S] of T.npz: one fit over whole sequences')
+    for k in ('w_t_root', 'w_t_pca', 'w_t_cam'):
+        ap.add_argument('--' + k, type=float, default=1.0, help='--sequences: the temporal weight of this group (not tuned on real tracks)')
+    ap.add_argument('--per_frame_shape', action='store_true', help='--sequences: betas per frame instead of one shape per (sequence, side)')
     opt = ap.parse_args(argv)
     if opt.bs < 1 or opt.iters < 0 or not -1 <= opt.center < 21:
         ap.error('--bs must be at least 1, --iters at least 0 and --center in -1 .. 20')
+    seq_len = smooth = None
     with np.load(opt.targets) as f:
         targets = read_targets(f)
+        if opt.sequences:
+            if 'seq_len' not in f:
+                ap.error('--sequences needs seq_len [S] in the targets')
+            seq_len = np.asarray(f['seq_len']).astype(np.int64).reshape(-1)
+            smooth = {'root': opt.w_t_root, 'pca': opt.w_t_pca, 'cam': opt.w_t_cam}
+            if min(smooth.values()) < 0:
+                ap.error('--w_t_root, --w_t_pca and --w_t_cam must be >= 0')
     state = checkpoint_weights(torch.load(opt.model, map_location='cpu', weights_only=False), opt.ema, opt.model)
     tables, keep = tables_from_checkpoint(state, opt.center)
     lr = {g: (getattr(opt, 'lr_' + g) if getattr(opt, 'lr_' + g) is not None else opt.lr) for g in ('root', 'pca', 'betas', 'cam')}
     weights = {k: getattr(opt, k) for k in ('w_verts', 'w_joints', 'w_uv', 'w_pca', 'w_beta', 'w_init') if getattr(opt, k) is not None}
     t0 = time.perf_counter()
-    res = fit_targets(tables, targets, opt.iters, lr, weights, opt.bs, opt.cam_scale, start=opt.start)
+    res = fit_targets(tables, targets, opt.iters, lr, weights, opt.bs, opt.cam_scale, start=opt.start, seq_len=seq_len, smooth=smooth,
+                      share_betas=not opt.per_frame_shape)
     torch.cuda.synchronize()
     sec = time.perf_counter() - t0
     np.savez(opt.out, **{'%s_%s' % (k, s): v for s, d in res.items() for k, v in d.items()})

@@ -9,10 +9,10 @@
 //
 // The forward and the backward are mano_device.h's phases, the ones mano.hip and mano_bwd.hip run (the outputs at iters = 0 are
 // dir_mano_forward's bits); unlike dir_mano_backward_pair this entry point accepts the root_palm wrist.  The residuals, the mean squared
-// errors and the Adam step are this kernel's own.
+// errors and the Adam step are mano_fit_device.h's, shared with the sequence fit (mano_fit_seq.hip).
 // fp32 throughout, every reduction in a fixed order, no atomics, no scratch buffer: a row gives the same bits in any slot of any batch and
 // in either hand slot.
-#include "mano_device.h"
+#include "mano_fit_device.h"
 
 namespace {
 
@@ -114,60 +114,15 @@ __global__ __launch_bounds__(BT) void mano_fit_kernel(FitArgs args) {
 
         // ================================================================ residuals: the cotangents gV, gJ, gU; the mean squared residuals at p0 and at the end
         const bool last = it >= n_it, want_mse = it == 0 || last;
-        const float sc = s_cam[0], tx = s_cam[1], ty = s_cam[2];
         float red[11] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};     // sum g.x, g.y, g.z | g s | g tx, g ty | sq V | sq J, n J | sq U, n U
-        for (int v = tid; v < NV; v += BT) {
-            float gx = 0.f, gy = 0.f, gz = 0.f;
-            if (use_v) {
-                const float* t = a.verts_t + (b * NV + v) * 3;
-                const float dx = (s_vert[3 * v] - L.c[0]) - t[0], dy = (s_vert[3 * v + 1] - L.c[1]) - t[1], dz = (s_vert[3 * v + 2] - L.c[2]) - t[2];
-                gx = args.kv * dx; gy = args.kv * dy; gz = args.kv * dz;
-                red[6] += dx * dx + dy * dy + dz * dz;
-            }
-            s_gv[3 * v] = gx; s_gv[3 * v + 1] = gy; s_gv[3 * v + 2] = gz;
-            red[0] += gx; red[1] += gy; red[2] += gz;
-        }
-        if (tid < 21) {
-            float gx = 0.f, gy = 0.f, gz = 0.f;
-            const float jx = L.jtr[3 * tid] - L.c[0], jy = L.jtr[3 * tid + 1] - L.c[1], jz = L.jtr[3 * tid + 2] - L.c[2];
-            if (use_j) {
-                const float c = a.joints_conf ? a.joints_conf[b * 21 + tid] : 1.f;
-                if (c > 0.f) {                                   // selected, never multiplied by 0: the target may hold NaN
-                    const float* t = a.joints_t + (b * 21 + tid) * 3;
-                    const float dx = jx - t[0], dy = jy - t[1], dz = jz - t[2], k = args.kj * c;
-                    gx = k * dx; gy = k * dy; gz = k * dz;
-                    red[7] += dx * dx + dy * dy + dz * dz; red[8] += 1.f;
-                }
-            }
-            if (use_uv) {
-                const float d = a.uv_conf ? a.uv_conf[b * 21 + tid] : 1.f;
-                if (d > 0.f) {
-                    const float* t = a.uv_t + (b * 21 + tid) * 2;
-                    const float ex = (sc * jx + tx) - t[0], ey = (sc * jy + ty) - t[1], k = args.kuv * d;
-                    const float g0 = k * ex, g1 = k * ey;
-                    red[3] += g0 * jx + g1 * jy;
-                    red[4] += g0; red[5] += g1;
-                    gx = fmaf(sc, g0, gx); gy = fmaf(sc, g1, gy);
-                    red[9] += ex * ex + ey * ey; red[10] += 1.f;
-                }
-            }
-            G.gj[3 * tid] = gx; G.gj[3 * tid + 1] = gy; G.gj[3 * tid + 2] = gz;
-            red[0] += gx; red[1] += gy; red[2] += gz;
-        }
-#pragma unroll
-        for (int e = 0; e < 6; ++e) { const float s = dir::wave_sum_dpp(red[e]); if (lane == 0) s_red[wave][e] = s; }
-        if (want_mse) {
-#pragma unroll
-            for (int e = 6; e < 11; ++e) { const float s = dir::wave_sum_dpp(red[e]); if (lane == 0) s_red[wave][e] = s; }
-        }
+        fit::residuals(a, b, L, G, s_vert, s_gv, s_cam, use_v, use_j, use_uv, args.kv, args.kj, args.kuv, tid, red);
+        fit::residual_partials(red, want_mse, s_red, lane, wave);
         if (tid < 48) { G.gAt[tid] = 0.f; }
         __syncthreads();
         if (tid < 11) s_sum[tid] = s_red[0][tid] + s_red[1][tid] + s_red[2][tid] + s_red[3][tid];
         __syncthreads();
         if (want_mse && tid < 3) {
-            const float sq = tid == 0 ? s_sum[6] : tid == 1 ? s_sum[7] : s_sum[9];
-            const float n = tid == 0 ? (use_v ? 778.f : 0.f) : tid == 1 ? s_sum[8] : s_sum[10];
-            const float mse = n > 0.f ? sq / n : 0.f;
+            const float mse = fit::mean_sq(s_sum, use_v, tid);
             if (it == 0) s_mse[tid] = mse;
             if (last) s_mse[3 + tid] = mse;
         }
@@ -206,18 +161,10 @@ __global__ __launch_bounds__(BT) void mano_fit_kernel(FitArgs args) {
         int bad = 0;
         const float pb1n = pb1 * args.b1, pb2n = pb2 * args.b2;
         if (tid < 64) {
-#pragma clang fp contract(off)
             const float p = s_p[tid];
-            float g = s_g[tid];
-            if (tid >= 6 && tid < 51) g = g + args.k_pca * p;
-            if (tid >= 51 && tid < 61) g = g + args.k_beta * p;
-            g = g + args.k_init * (p - s_anchor[tid]);
-            m_new = args.b1 * s_m[tid] + (1.f - args.b1) * g;
-            v_new = args.b2 * s_vv[tid] + (1.f - args.b2) * (g * g);
-            const float lr = args.lr[tid < 6 ? 0 : tid < 51 ? 1 : tid < 61 ? 2 : 3];
-            const float mhat = m_new / (1.f - pb1n), vhat = v_new / (1.f - pb2n);
-            p_new = lr == 0.f ? p : p - (lr * mhat) / (sqrtf(vhat) + args.eps);
-            bad = !finite(p_new) || !finite(m_new) || !finite(v_new);
+            const float g = fit::prior_gradient(tid, s_g[tid], p, s_anchor[tid], args.k_pca, args.k_beta, args.k_init);
+            p_new = p; m_new = s_m[tid]; v_new = s_vv[tid];
+            bad = !fit::adam(g, args.lr[fit::group_of(tid)], args.b1, args.b2, args.eps, pb1n, pb2n, p_new, m_new, v_new);
         }
         if (__syncthreads_or(bad)) {          // the step is not taken: the last finite iterate and its state stay, and the loop ends
             status |= 4;

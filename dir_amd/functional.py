@@ -403,3 +403,69 @@ def mano_fit_start(tables_lr, init_lr, verts=None, joints=None, joints_conf=None
         _capi.check(_capi.lib().dir_mano_fit_start((_capi.ManoTables * hands)(*tables_lr), (_capi.ManoFitStartHand * hands)(*hs), C.byref(opts), hands, B,
                                                    _capi.stream_ptr()), 'dir_mano_fit_start')
     return res
+
+
+def mano_fit_sequence_workspace_bytes(N, S, hands):
+    """dir_mano_fit_sequence_workspace_bytes: the bytes of `work` for N frames in S sequences (0: bad arguments)"""
+    return int(_capi.lib().dir_mano_fit_sequence_workspace_bytes(int(N), int(S), int(hands)))
+
+
+def mano_fit_sequence(tables_lr, init_lr, seq_start, verts=None, joints=None, joints_conf=None, joint_uv=None, uv_conf=None, iters=200, lr=(0.1, 0.1, 0.1, 0.1),
+                      weights=None, smooth=(0.0, 0.0, 0.0), share_betas=True, betas=(0.9, 0.999), eps=1e-8, anchor=None, state=None, seq_state=None,
+                      outputs=True, para_out=None, work=None, seq_start_host=None):
+    """dir_mano_fit_sequence (include/dir_hip.h, "MANO fitting: sequences").  Arguments as mano_fit's, with N frames for B; seq_start: int32 [S+1] on the
+    GPU; smooth: (w_t_root, w_t_pca, w_t_cam); seq_state: None, or a list with one float32 [S, MANO_FIT_SEQ_STATE] tensor or None per hand (updated in
+    place, as state); work: a uint8 GPU tensor of at least mano_fit_sequence_workspace_bytes (None: allocated here by torch, nothing inside the call
+    allocates); seq_start_host: an optional sequence of S+1 ints the entry point checks on the host.  -> (list per hand of dicts para, mse [N,6], status [N]
+    (+ verts, joints, joint_uv with outputs), seq_status int32 [hands, S])."""
+    import ctypes as C
+    hands = len(init_lr)
+    assert hands in (1, 2) and len(tables_lr) == hands
+    N, dev = init_lr[0].shape[0], init_lr[0].device
+    if not (seq_start.dtype == torch.int32 and seq_start.is_contiguous() and seq_start.dim() == 1 and seq_start.numel() >= 2 and seq_start.device == dev):
+        raise _capi.DirHipError('mano_fit_sequence: seq_start must be a contiguous int32 [S+1] tensor on %s' % dev)
+    S = seq_start.numel() - 1
+
+    def per_hand(ts, shape, what):
+        ts = [None] * hands if ts is None else list(ts)
+        assert len(ts) == hands
+        for t in ts:
+            if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape and t.device == dev):
+                raise _capi.DirHipError('mano_fit_sequence: %s must be a contiguous float32 %s tensor on %s' % (what, list(shape), dev))
+        _capi.require_cuda(*ts)
+        return ts
+    init = per_hand(init_lr, (N, 64), 'init')
+    tv, tj, cj = per_hand(verts, (N, 778, 3), 'verts'), per_hand(joints, (N, 21, 3), 'joints'), per_hand(joints_conf, (N, 21), 'joints_conf')
+    tu, cu = per_hand(joint_uv, (N, 21, 2), 'joint_uv'), per_hand(uv_conf, (N, 21), 'uv_conf')
+    an, st, po = per_hand(anchor, (N, 64), 'anchor'), per_hand(state, (N, _capi.MANO_FIT_STATE), 'state'), per_hand(para_out, (N, 64), 'para_out')
+    sst = per_hand(seq_state, (S, _capi.MANO_FIT_SEQ_STATE), 'seq_state')
+    w = dict(weights or {})
+    if set(w) - set(MANO_FIT_WEIGHTS):
+        raise ValueError('mano_fit_sequence: unknown weights %s' % sorted(set(w) - set(MANO_FIT_WEIGHTS)))
+    opts = _capi.ManoFitOpts(*[float(w.get(k, 0.0)) for k in MANO_FIT_WEIGHTS], (C.c_float * 4)(*[float(v) for v in lr]), float(betas[0]), float(betas[1]),
+                             float(eps), int(iters))
+    host = None if seq_start_host is None else (C.c_int32 * (S + 1))(*[int(v) for v in seq_start_host])
+    sopts = _capi.ManoFitSeqOpts(float(smooth[0]), float(smooth[1]), float(smooth[2]), int(bool(share_betas)),
+                                 None if host is None else C.cast(host, C.POINTER(C.c_int32)),
+                                 (C.c_void_p * 2)(*([None if t is None else t.data_ptr() for t in sst] + [None] * (2 - hands))))
+    need = mano_fit_sequence_workspace_bytes(N, S, hands)
+    if work is None:
+        work = torch.empty(max(need, 4), dtype=torch.uint8, device=dev)
+    if not (work.dtype == torch.uint8 and work.is_contiguous() and work.device == dev):
+        raise _capi.DirHipError('mano_fit_sequence: work must be a contiguous uint8 tensor on %s' % dev)
+    seq_status = torch.empty(hands, S, dtype=torch.int32, device=dev)
+    res, hs = [], []
+    P = _capi.ptr
+    for h in range(hands):
+        r = {'para': po[h] if po[h] is not None else torch.empty(N, 64, device=dev), 'mse': torch.empty(N, 6, device=dev),
+             'status': torch.empty(N, dtype=torch.int32, device=dev)}
+        if outputs:
+            r.update(verts=torch.empty(N, 778, 3, device=dev), joints=torch.empty(N, 21, 3, device=dev), joint_uv=torch.empty(N, 21, 2, device=dev))
+        hs.append(_capi.ManoFitHand(init[h].data_ptr(), P(an[h]), r['para'].data_ptr(), P(tv[h]), P(tj[h]), P(cj[h]), P(tu[h]), P(cu[h]),
+                                    P(r.get('verts')), P(r.get('joints')), P(r.get('joint_uv')), r['mse'].data_ptr(), r['status'].data_ptr(), P(st[h])))
+        res.append(r)
+    with torch.cuda.device(dev):
+        _capi.check(_capi.lib().dir_mano_fit_sequence((_capi.ManoTables * hands)(*tables_lr), (_capi.ManoFitHand * hands)(*hs), C.byref(opts), C.byref(sopts),
+                                                      seq_start.data_ptr(), S, N, hands, seq_status.data_ptr(), work.data_ptr(), work.numel(),
+                                                      _capi.stream_ptr()), 'dir_mano_fit_sequence')
+    return res, seq_status

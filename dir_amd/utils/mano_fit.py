@@ -16,6 +16,13 @@ tuned on real MANO tables or real keypoints.
 The start (include/dir_hip.h, "MANO fitting: closed-form start") turns the root onto 3-D targets by a rigid alignment of the points that are
 rigid under it, or, with 2-D targets alone, picks one of the cube's 24 rotations, and fits the camera by least squares: an arbitrary rotation
 is no longer out of Adam's reach, and cam_scale need not be guessed.
+
+    res = fit_mano_sequence(layer, neutral_para(N), seq_lengths, joints=tracks, joints_conf=conf, smooth={'root': 1, 'pca': 1, 'cam': 1})
+    res.para [N,64] (one shape per sequence in every frame's 51:61), ..., res.seq_status [S]
+
+Whole sequences (include/dir_hip.h, "MANO fitting: sequences"; csrc/mano_fit_seq.hip): the N frames of S sequences laid end to end are ONE optimisation --
+one shape per (sequence, hand), a pose and a camera per frame, neighbouring frames coupled in time -- so the betas do not change from frame to frame and a
+frame without keypoints is filled from its neighbours.  One launch per iteration (two with the shared shape), all enqueued by one library call.
 """
 import collections
 
@@ -129,3 +136,73 @@ def fit_mano(layer_or_tables, init, verts=None, joints=None, joints_conf=None, j
     rs = [FitResult(r['para'], r.get('verts'), r.get('joints'), r.get('joint_uv'), r['mse'][:, :3], r['mse'][:, 3:], r['status'],
                     None if st is None else st[h]) for h, r in enumerate(res)]
     return FitResult(*[list(f) for f in zip(*rs)]) if pair else rs[0]
+
+
+# ---- whole sequences: dir_mano_fit_sequence (csrc/mano_fit_seq.hip; include/dir_hip.h, "MANO fitting: sequences")
+DEFAULT_SMOOTH = {'root': 1.0, 'pca': 1.0, 'cam': 1.0}       # w_t_root, w_t_pca, w_t_cam: NOT tuned on real tracks
+STATUS_NO_DATA = 8                                           # fit_mano_sequence only: a non-finite target in use, the frame's data terms were dropped
+SEQ_STATUS_EMPTY, SEQ_STATUS_SHAPE_FROZEN = 2, 4
+SeqFitResult = collections.namedtuple('SeqFitResult', FitResult._fields + ('seq_status',))
+SeqState = collections.namedtuple('SeqState', 'frames seq')  # the frames' Adam state [N,132] and the shared shapes' [S,24] (lists of two for a pair)
+
+
+def new_seq_state(N, S, hands=1, device='cuda'):
+    """a fresh state for fit_mano_sequence: all zeros"""
+    fr = [torch.zeros(N, _capi.MANO_FIT_STATE, device=device) for _ in range(hands)]
+    sq = [torch.zeros(S, _capi.MANO_FIT_SEQ_STATE, device=device) for _ in range(hands)]
+    return SeqState(fr, sq) if hands == 2 else SeqState(fr[0], sq[0])
+
+
+def fit_mano_sequence(layer_or_tables, init, seq_lengths, verts=None, joints=None, joints_conf=None, joint_uv=None, uv_conf=None, iters=200, lr=0.1,
+                      weights=None, smooth=None, share_betas=True, state=None, outputs=True, anchor=None, betas=(0.9, 0.999), eps=1e-8, start='neutral',
+                      work=None):
+    """dir_mano_fit_sequence: one optimisation over whole sequences.  init [N,64] and the targets as fit_mano's, with the N frames of the sequences laid
+    end to end; seq_lengths: their lengths (ints on the host, each >= 1, summing to N).  One shape per (sequence, hand) with share_betas (else one per
+    frame), a pose and a camera per frame, and the temporal term `smooth` = {'root':, 'pca':, 'cam':} (None: DEFAULT_SMOOTH; a missing key is 0) between
+    neighbouring frames.  A frame whose confidences are all 0 is filled from its neighbours; a frame with a non-finite init passes through and splits its
+    sequence.  state: True for a fresh one, or the SeqState of an earlier result (updated in place; pass the same `anchor`).  start: 'neutral', or
+    'closed': start_mano(init, the same targets and weights) runs per frame first, and its parameters are the anchor where none is given.  work: a uint8
+    workspace of functional.mano_fit_sequence_workspace_bytes to reuse.  -> SeqFitResult: fit_mano's fields over the N frames (para holds the sequence's
+    betas in every frame) + seq_status [S] (2: no usable frame, 4: the shared shape was frozen); lists of two per field for a pair."""
+    if start not in ('neutral', 'closed'):
+        raise ValueError("fit_mano_sequence: start is 'neutral' or 'closed', got %r" % (start,))
+    if start == 'closed':
+        init = start_mano(layer_or_tables, init, verts, joints, joints_conf, joint_uv, uv_conf, weights).para
+        anchor = init if anchor is None else anchor
+    pair = isinstance(layer_or_tables, (list, tuple))
+    hands = 2 if pair else 1
+    ls = lambda x: list(x) if pair else [x]  # noqa: E731
+    opt = lambda x: None if x is None else [None if t is None else _capi.f32c(t) for t in ls(x)]  # noqa: E731
+    tabs = [_tables(x) for x in ls(layer_or_tables)]
+    p0 = [_capi.f32c(t) for t in ls(init)]
+    if len(tabs) != hands or len(p0) != hands:
+        raise ValueError('fit_mano_sequence: a pair takes lists of two')
+    N, dev = p0[0].shape[0], p0[0].device
+    lengths = [int(n) for n in seq_lengths]
+    if any(n < 1 for n in lengths) or sum(lengths) != N:
+        raise ValueError('fit_mano_sequence: seq_lengths must be >= 1 and sum to the %d frames, got %s' % (N, lengths[:8]))
+    S = len(lengths)
+    smooth = DEFAULT_SMOOTH if smooth is None else smooth
+    if set(smooth) - set(DEFAULT_SMOOTH):
+        raise ValueError('fit_mano_sequence: smooth keys are %s, got %s' % (sorted(DEFAULT_SMOOTH), sorted(smooth)))
+    weights = _term_weights(weights, verts, joints, joint_uv)
+    if state is True:
+        state = new_seq_state(N, S, hands, dev)
+    fr, sq = (None, None) if state is None else (ls(state.frames), ls(state.seq))
+    starts = [0]
+    for n in lengths:
+        starts.append(starts[-1] + n)
+    if N == 0:
+        e = lambda *s: torch.empty((0,) + s, device=dev)  # noqa: E731
+        rs = [SeqFitResult(p.clone(), e(778, 3), e(21, 3), e(21, 2), e(3), e(3), torch.empty(0, dtype=torch.int32, device=dev), state,
+                           torch.empty(0, dtype=torch.int32, device=dev)) for p in p0]
+        return SeqFitResult(*[list(f) for f in zip(*rs)]) if pair else rs[0]
+    res, seq_status = F.mano_fit_sequence(tabs, p0, torch.tensor(starts, dtype=torch.int32).to(dev), opt(verts), opt(joints), opt(joints_conf), opt(joint_uv),
+                                          opt(uv_conf), iters, _lr4(lr), weights, [float(smooth.get(k, 0.0)) for k in ('root', 'pca', 'cam')], share_betas, betas,
+                                          eps, opt(anchor), fr, sq, outputs, work=work, seq_start_host=starts)
+    rs = [SeqFitResult(r['para'], r.get('verts'), r.get('joints'), r.get('joint_uv'), r['mse'][:, :3], r['mse'][:, 3:], r['status'],
+                       None if state is None else SeqState(fr[h], sq[h]), seq_status[h]) for h, r in enumerate(res)]
+    if not pair:
+        return rs[0]
+    out = SeqFitResult(*[list(f) for f in zip(*rs)])
+    return out._replace(state=state)

@@ -29,7 +29,7 @@ extern "C" {
 #define DIR_E_LAUNCH (-2)   /* hipLaunchKernel / HIP runtime error          */
 #define DIR_E_NODEVICE (-3) /* no gfx950 device visible                     */
 
-#define DIR_ABI_VERSION 55
+#define DIR_ABI_VERSION 56
 
 int dir_abi_version(void);
 const char* dir_last_error(void);
@@ -250,6 +250,77 @@ typedef struct dir_mano_fit_start_opts {
 /* tables_host / hands_host: HOST arrays of `hands` (1 or 2) entries; grid = B x hands.  Enqueued on `stream`. */
 int dir_mano_fit_start(const dir_mano_tables* tables_host, const dir_mano_fit_start_hand* hands_host, const dir_mano_fit_start_opts* opts_host,
                        int hands, int B, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * MANO fitting: sequences (ABI 56; csrc/mano_fit_seq.hip; nothing in the reference).  dir_mano_fit fits every row alone.  Keypoint tracks come as
+ * sequences of one person: dir_mano_fit_sequence is ONE optimisation over a batch of sequences that keeps one shape per (sequence, hand), a pose
+ * and a camera per frame, and couples neighbouring frames in time.  tests/helpers/mano_seq_fit_ref.py restates the rule in torch.
+ *
+ * A batch is S sequences laid end to end: seq_start [S+1] int32 ON THE DEVICE, ascending, seq_start[0] = 0, seq_start[S] = N; frames
+ * seq_start[s] .. seq_start[s+1] - 1 are sequence s (a sequence may have length 1).  The arrays of dir_mano_fit_hand have N rows.
+ *
+ * Frame classes, decided once from the inputs (bits of `status`):
+ *   inert    (bit 1)      p0 or `anchor` non-finite.  The frame passes through as dir_mano_fit's bit-1 rows do (p_out = p0 bit for bit, state untouched,
+ *                         outputs the forward at p0, or 0 where p0 is non-finite, mse 0).  It is in no chain: no temporal edge touches it, its two
+ *                         neighbours do NOT become neighbours of each other, and it gives nothing to the shared shape.
+ *   no data  (bit 3 = 8)  a target in use (dir_mano_fit's definition) is non-finite: every data term of the frame is dropped; it stays in the chain, and
+ *                         priors, temporal terms and the shared shape still move it.  A frame whose confidences are all 0 behaves the same way and
+ *                         sets no bit: that is how missing frames are filled.
+ * An EDGE joins frames t - 1 and t of one sequence when neither is inert.
+ *
+ * Variables of one (sequence, hand): per frame the 54 floats root 0:6 | PCA 6:51 | cam 61:64, and the betas 51:61 -- one 10-vector b per sequence with
+ * share_betas != 0 (start and prior centre: p0's / anchor's betas of the sequence's first frame that is not inert), else 10 per frame as dir_mano_fit.
+ *
+ *   E = sum_t E_data(p_t)            dir_mano_fit's E with the same dir_mano_fit_opts; with share_betas the terms w_beta |b|^2 and w_init |b - a_b|^2
+ *                                    enter once per sequence, not once per frame
+ *     + sum over edges (t-1, t):     w_t_root |R(p_t) - R(p_{t-1})|_F^2  +  w_t_pca |p_t[6:51] - p_{t-1}[6:51]|^2  +  w_t_cam |p_t[61:64] - p_{t-1}[61:64]|^2
+ *   R = the robust-6D rotation of the six root floats (dir_mano_forward's): a chordal distance, independent of the scale of the unnormalised 6D input.
+ *
+ * One iteration = one Adam step on E for every frame at once, every gradient taken at iterate k: the iterates live in two copies in the workspace, a
+ * frame reads itself and its neighbours from copy k & 1 and writes copy (k + 1) & 1, and a launch boundary separates the iterations (no grid barrier,
+ * no flags).  Per frame and iteration, fp32 throughout:
+ *   1-3. dir_mano_fit's steps 1-3 (with share_betas the forward runs at the sequence's b), with one addition before the robust-6D chain rule: with
+ *        w_t_root > 0 the 3x3 root cotangent G gets, element by element, G = G + k_r (R - R_prev) where the edge to t - 1 exists, then
+ *        G = G + k_r (R - R_next) where the edge to t + 1 exists; k_r = 2 w_t_root; R_prev / R_next = robust 6D of the neighbour's six floats;
+ *   4.   dir_mano_fit's step 4 (with share_betas the ten betas are left out: step 6), then for i in 6:51 with w_t_pca > 0:
+ *        g_i = g_i + k_p (p_i - prev_i) where the edge to t - 1 exists, then g_i = g_i + k_p (p_i - next_i) where the edge to t + 1 exists, k_p = 2 w_t_pca;
+ *        the same for i in 61:64 with k_c = 2 w_t_cam.  Each product and sum rounded (no FMA contraction).  A term whose weight is 0 and a missing
+ *        edge are SKIPPED, never multiplied by 0: with the three weights 0 and share_betas = 0 every frame gives dir_mano_fit's bits;
+ *   5.   dir_mano_fit's step 5 on the frame's components (54 with share_betas: m and v of 51:61 in the frame's state stay as they are).  A step
+ *        that gives a non-finite p, m or v is not taken: status bit 2, the frame is FROZEN at that iterate for the rest of the call (its neighbours
+ *        still see it; it gives nothing further to the shape).
+ *   6.   With share_betas, per (sequence, hand) after all frames' step 5: g_b[k] = the sum over the sequence's frames that are neither inert nor
+ *        frozen (the one frozen in this iteration included in "frozen") of the backward's d E_data / d betas[k] taken at b -- a fixed tree that depends
+ *        on the sequence's length only: lane l of 256 adds frames l, l + 256, ... (index within the sequence) in order, excluded frames adding 0.f,
+ *        each 64-lane wave sums its lanes (the DPP tree of dir_mano_fit) and the four waves are added in order; no atomics.  Then
+ *        g_b = g_b + (2 w_beta) b, g_b = g_b + (2 w_init) (b - a_b), and step 5 on b with lr[2] and the sequence's own m, v, P1, P2.  A non-finite step
+ *        is not taken and freezes the shape for the rest of the call (seq_status bit 2).  Every frame of iterate k + 1 reads the same ten floats.
+ *
+ * iters is fixed: no early stop, no host read; the whole call is 2 + iters (1 + (share_betas != 0)) + 1 launches on `stream` and can be captured in a graph.
+ *
+ * Outputs (dir_mano_fit_hand's, N rows): p_out (with share_betas the sequence's b in every frame's 51:61 that is not inert; may alias p0), verts /
+ * joints / joint_uv at the returned p, mse [N,6] as dir_mano_fit (a no-data frame: 0), status [N]: bit 0 reflection, 1 inert, 2 frozen, 3 no data.
+ * state [N, DIR_MANO_FIT_STATE] (optional, in and out) as dir_mano_fit; seq_state (optional, in and out, per hand [S, DIR_MANO_FIT_SEQ_STATE]):
+ * m [10] | v [10] | P1 | P2 | t (the int32's bits) | 0 of the shared shape, all zeros = fresh.  With both (and the anchor held fixed), iters = a then
+ * iters = b from the first call's p_out equals iters = a + b bit for bit.
+ * seq_status [hands, S] int32 (optional): bit 1 = the sequence has no frame in a chain, bit 2 = its shared shape was frozen.
+ * A sequence gives the same bits alone, in any slot of any ragged batch, and in either hand slot. */
+#define DIR_MANO_FIT_SEQ_STATE 24
+#define DIR_MANO_FIT_SEQ_LANES 256 /* the width of step 6's tree */
+typedef struct dir_mano_fit_seq_opts {
+    float w_t_root, w_t_pca, w_t_cam;   /* >= 0; 0 = the term is absent                                                            */
+    int32_t share_betas;                /* != 0: one shape per (sequence, hand)                                                     */
+    const int32_t* seq_start_host;      /* optional HOST copy of seq_start [S+1]: when given it is checked (0, ascending, N at the end) */
+    float* seq_state[2];                /* per hand: [S, DIR_MANO_FIT_SEQ_STATE] in and out, or NULL                               */
+} dir_mano_fit_seq_opts;
+/* bytes of `work` for N frames in S sequences (0 on bad arguments).  The contents need no initialisation and mean nothing afterwards. */
+size_t dir_mano_fit_sequence_workspace_bytes(int N, int S, int hands);
+/* tables_host / hands_host: HOST arrays of `hands` (1 or 2) entries.  seq_start, seq_status, work: device.  Nothing is allocated; a workspace smaller
+ * than the query, negative or non-finite weights, or a seq_start_host that is not ascending from 0 to N return DIR_E_INVALID before any launch.  A
+ * seq_start on the device that breaks the rule cannot fault (every index is clamped to the N frames) but fits unspecified chains. */
+int dir_mano_fit_sequence(const dir_mano_tables* tables_host, const dir_mano_fit_hand* hands_host, const dir_mano_fit_opts* opts_host,
+                          const dir_mano_fit_seq_opts* seq_opts_host, const int32_t* seq_start, int S, int N, int hands, int32_t* seq_status,
+                          void* work, size_t work_bytes, void* stream);
 
 /* Backward of RegressorOffset's three Linears (models/dir.py:339-351).  w_left / w_right [64][1408], w_offset [3][2691]: the
  * nn.Linear weights in their own layout; tok [B,42,64] = the STE head output (tokens 0..20 left); prev_* the previous stage's
