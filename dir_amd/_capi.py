@@ -42,6 +42,18 @@ class ManoFitSeqOpts(C.Structure):     # dir_mano_fit_seq_opts
                                                                                ('seq_state', C.c_void_p * 2)]
 
 
+class ManoFitPairArgs(C.Structure):    # dir_mano_fit_pair_args
+    _fields_ = [(n, C.c_void_p) for n in ('o0', 'o_target', 'o_conf', 'o_anchor')] + [('radii', C.c_void_p * 2)] + [
+        (n, C.c_void_p) for n in ('offset_out', 'col', 'pair_status', 'o_state')]
+
+
+class ManoFitPairOpts(C.Structure):    # dir_mano_fit_pair_opts
+    _fields_ = [(n, C.c_float) for n in ('w_col', 'w_off', 'w_off_init', 'lr_o')]
+
+
+MANO_FIT_PAIR_STATE = 12  # DIR_MANO_FIT_PAIR_STATE
+
+
 class ManoFitStartHand(C.Structure):   # dir_mano_fit_start_hand
     _fields_ = [(n, C.c_void_p) for n in ('p0', 'p_out', 'verts_t', 'joints_t', 'joints_conf', 'uv_t', 'uv_conf', 'status', 'choice', 'info')]
 
@@ -193,7 +205,7 @@ class RenderLights(C.Structure):         # dir_render_lights
                 ('shininess', C.c_float)]
 
 
-ABI_VERSION = 56         # DIR_ABI_VERSION (include/dir_hip.h)
+ABI_VERSION = 57         # DIR_ABI_VERSION (include/dir_hip.h)
 DT_F32, DT_BF16, DT_F16X3, DT_F16X1, DT_F16X3P, DT_F16X1P, DT_F16 = 0, 1, 3, 4, 5, 6, 7      # DT_F16: f16 STORAGE (round 5)
 CONV_RELU, CONV_PRE_RELU = 1, 2
 
@@ -273,6 +285,8 @@ _SIGNATURES = {
     'dir_mano_forward_pair': (C.c_int, [C.POINTER(ManoTables), _p, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _i, _p]),
     'dir_mano_backward_pair': (C.c_int, [C.POINTER(ManoTables), _p, _i, _p, _i, _p, _i, _p, _p, _p, _p, _p, _i, _p, _i, _p, _i, _i, _i, _p]),
     'dir_mano_fit': (C.c_int, [C.POINTER(ManoTables), C.POINTER(ManoFitHand), C.POINTER(ManoFitOpts), _i, _i, _p]),
+    'dir_mano_fit_pair': (C.c_int, [C.POINTER(ManoTables), C.POINTER(ManoFitHand), C.POINTER(ManoFitOpts), C.POINTER(ManoFitPairArgs),
+                                    C.POINTER(ManoFitPairOpts), _i, _p]),
     'dir_mano_fit_start': (C.c_int, [C.POINTER(ManoTables), C.POINTER(ManoFitStartHand), C.POINTER(ManoFitStartOpts), _i, _i, _p]),
     'dir_mano_fit_sequence_workspace_bytes': (C.c_size_t, [_i, _i, _i]),
     'dir_mano_fit_sequence': (C.c_int, [C.POINTER(ManoTables), C.POINTER(ManoFitHand), C.POINTER(ManoFitOpts), C.POINTER(ManoFitSeqOpts), _p, _i, _i, _i, _p,

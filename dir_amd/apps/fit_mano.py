@@ -4,6 +4,7 @@
     python -m dir_amd.apps.fit_mano --model CKPT --targets T.npz --out O.npz [--iters 200] [--lr 0.1] [--lr_root --lr_pca --lr_betas --lr_cam]
                                     [--bs 256] [--center 0] [--cam_scale 1.0] [--w_verts 1e4 --w_joints 1e4 --w_uv 1 --w_pca 0 --w_beta 0
                                     --w_init 0] [--ema] [--start neutral|closed] [--sequences [--w_t_root 1 --w_t_pca 1 --w_t_cam 1] [--per_frame_shape]]
+                                    [--pair [--w_col 1e4 --w_offset 0 --w_offset_init 0 --lr_offset LR --radii FILE|auto]]
 
 The MANO tables come from the checkpoint (init_regressor.mano_layer_{left,right}.th_*), as in apps.predict.  T.npz holds, per side in
 (left, right), any of  verts_<side> [N,778,3],  joints_<side> [N,21,3] with joints_conf_<side> [N,21],  joint_uv_<side> [N,21,2] (the crop's
@@ -25,6 +26,15 @@ whose confidences are all 0 from its neighbours.  A batch takes whole sequences 
 betas_<side> [S,10] (the sequence's shape: para_<side>'s 51:61 of its first frame that did not pass through; NaN where there is none) and
 seq_status_<side> [S] (2: no usable frame, 4: the shape was frozen); status_<side> gains bit 3 (a non-finite target in use: the frame's data terms were
 dropped).  Without --sequences every byte written is what it is without these flags.  The temporal defaults are NOT tuned on real tracks.
+
+--pair: row n of the left side and row n of the right side are the two hands of one person, fitted TOGETHER (dir_mano_fit_pair, utils/mano_fit.py
+fit_mano_pair): the offset o [N,3] between them (right centre joint minus left, metres, camera axes; 0.15 x pd_offset) is a further variable, and a
+capsule per bone keeps the hands from passing through each other (--w_col).  T.npz may carry offset [N,3] (the start and, with --w_offset, the target;
+default 0) with offset_conf [N]; --w_offset_init pulls o to its start, --lr_offset is its rate (default --lr).  --radii auto: capsule_radii of the
+checkpoint's tables; a FILE.npz holds radii_left and radii_right [20].  Both sides need a target and the same N; --center must be >= 0; not with
+--sequences.  O.npz gains offset [N,3], collision [N,4] (mean squared and largest capsule overlap in metres before, then after) and pair_status [N]
+(1: a hand passed through, 2: offset or radii non-finite -- the coupling was off; 4: the offset was frozen; 8: crossing bones met).  Without --pair
+every byte written is what it is without these flags.  The radii quantile and the weights are NOT tuned: this tree has no real MANO tables.
 """
 import time
 
@@ -146,6 +156,54 @@ def fit_targets(tables, targets, iters=200, lr=0.1, weights=None, bs=256, cam_sc
     return out
 
 
+def layer_buffers(state, side):
+    """what capsule_radii reads, from the checkpoint's th_* buffers of one side"""
+    pre = 'init_regressor.mano_layer_%s.' % side
+    return {'th_v_template': state[pre + 'th_v_template'].detach().cpu(), 'th_weights': state[pre + 'th_weights'].detach().cpu(),
+            'th_J_regressor': state[pre + 'th_J_regressor'].detach().cpu(), 'side': side}
+
+
+def fit_pair_targets(tables, targets, radii, offset=None, offset_conf=None, iters=200, lr=0.1, weights=None, bs=256, cam_scale=1.0, device='cuda',
+                     start='neutral'):
+    """both sides of read_targets' dict (the same N) fitted as pairs, one launch per batch -> (fit_targets' dict per side, {offset, collision,
+    pair_status}) (numpy).  radii: {side: [20] array}; offset [N,3] / offset_conf [N]: the start (default 0) and, with w_off, the target; lr: fit_mano_pair's
+    (a dict may hold 'offset'); weights: one dict over fit_mano's keys and w_col, w_off, w_off_init."""
+    import torch
+
+    from ..utils import mano_fit as MF
+    if sorted(targets) != sorted(SIDES) or len({next(iter(targets[s].values())).shape[0] for s in SIDES}) != 1:
+        raise ValueError('fit_mano: --pair needs targets for both sides with the same N')
+    N = next(iter(targets['left'].values())).shape[0]
+    if offset is not None and tuple(offset.shape) != (N, 3) or offset_conf is not None and (offset is None or tuple(offset_conf.shape) != (N,)):
+        raise ValueError('fit_mano: offset must be [N,3] and offset_conf [N] (with offset)')
+    rad = [torch.from_numpy(np.ascontiguousarray(np.asarray(radii[s], np.float32).reshape(20))).to(device) for s in SIDES]
+    w = dict(weights or {})
+    for k, t in (('w_verts', 'verts'), ('w_joints', 'joints'), ('w_uv', 'joint_uv')):
+        if not any(t in targets[s] for s in SIDES):
+            w[k] = 0.0
+        else:
+            w.setdefault(k, MF.DEFAULT_WEIGHTS[k])
+    for k, d in MF.DEFAULT_PAIR_WEIGHTS.items():
+        w.setdefault(k, d)
+    parts, pparts = {s: [] for s in SIDES}, []
+    for b0 in range(0, N, bs):
+        b1 = min(b0 + bs, N)
+        dev = lambda s, k: torch.from_numpy(np.ascontiguousarray(targets[s][k][b0:b1])).to(device) if k in targets[s] else None  # noqa: E731
+        arg = lambda k: [dev(s, k) for s in SIDES]  # noqa: E731
+        init = [dev(s, 'init') if 'init' in targets[s] else MF.neutral_para(b1 - b0, cam_scale, device) for s in SIDES]
+        o0 = torch.zeros(b1 - b0, 3, device=device) if offset is None else torch.from_numpy(np.ascontiguousarray(offset[b0:b1], np.float32)).to(device)
+        use_t = offset is not None and w['w_off'] > 0
+        oc = None if offset_conf is None or not use_t else torch.from_numpy(np.ascontiguousarray(offset_conf[b0:b1], np.float32)).to(device)
+        r = MF.fit_mano_pair([tables[s] for s in SIDES], init, o0, radii=rad, offset_target=o0 if use_t else None, offset_conf=oc, verts=arg('verts'),
+                             joints=arg('joints'), joints_conf=arg('joints_conf'), joint_uv=arg('joint_uv'), uv_conf=arg('uv_conf'), iters=iters, lr=lr, weights=w,
+                             start=start)
+        for h, s in enumerate(SIDES):
+            parts[s].append({k: getattr(r, k)[h].cpu().numpy() for k in ('para', 'verts', 'joints', 'joint_uv', 'mse_before', 'mse_after', 'status')})
+        pparts.append({'offset': r.offset.cpu().numpy(), 'collision': r.collision.cpu().numpy(), 'pair_status': r.pair_status.cpu().numpy()})
+    out = {s: {k: np.concatenate([p[k] for p in parts[s]]) for k in parts[s][0]} for s in SIDES}
+    return out, {k: np.concatenate([p[k] for p in pparts]) for k in pparts[0]}
+
+
 def main(argv=None):
     import argparse
 
@@ -171,12 +229,23 @@ def main(argv=None):
     for k in ('w_t_root', 'w_t_pca', 'w_t_cam'):
         ap.add_argument('--' + k, type=float, default=1.0, help='--sequences: the temporal weight of this group (not tuned on real tracks)')
     ap.add_argument('--per_frame_shape', action='store_true', help='--sequences: betas per frame instead of one shape per (sequence, side)')
+    ap.add_argument('--pair', action='store_true', help='row n of both sides is one person: fit the two hands together with their offset and a collision term')
+    ap.add_argument('--w_col', type=float, default=None, help='--pair: the weight of the capsule collision term (not tuned)')
+    ap.add_argument('--w_offset', type=float, default=0.0, help="--pair: the weight of the pull to the targets' offset")
+    ap.add_argument('--w_offset_init', type=float, default=0.0, help='--pair: the weight of the pull to the starting offset')
+    ap.add_argument('--lr_offset', type=float, default=None, help='--pair: the learning rate of the offset instead of --lr (0 freezes it)')
+    ap.add_argument('--radii', type=str, default='auto', help="--pair: 'auto' (capsule_radii of the checkpoint's tables) or an .npz with radii_left, radii_right [20]")
     opt = ap.parse_args(argv)
     if opt.bs < 1 or opt.iters < 0 or not -1 <= opt.center < 21:
         ap.error('--bs must be at least 1, --iters at least 0 and --center in -1 .. 20')
-    seq_len = smooth = None
+    if opt.pair and (opt.sequences or opt.center < 0):
+        ap.error('--pair needs --center >= 0 (the offset joins the two centre joints) and does not combine with --sequences')
+    seq_len = smooth = offset = offset_conf = None
     with np.load(opt.targets) as f:
         targets = read_targets(f)
+        if opt.pair:
+            offset = np.asarray(f['offset'], np.float32) if 'offset' in f else None
+            offset_conf = np.asarray(f['offset_conf'], np.float32) if 'offset_conf' in f else None
         if opt.sequences:
             if 'seq_len' not in f:
                 ap.error('--sequences needs seq_len [S] in the targets')
@@ -188,17 +257,33 @@ def main(argv=None):
     tables, keep = tables_from_checkpoint(state, opt.center)
     lr = {g: (getattr(opt, 'lr_' + g) if getattr(opt, 'lr_' + g) is not None else opt.lr) for g in ('root', 'pca', 'betas', 'cam')}
     weights = {k: getattr(opt, k) for k in ('w_verts', 'w_joints', 'w_uv', 'w_pca', 'w_beta', 'w_init') if getattr(opt, k) is not None}
+    extra = {}
+    if opt.pair:
+        from ..utils import mano_fit as MF
+        if opt.radii == 'auto':
+            radii = {s: MF.capsule_radii(layer_buffers(state, s)).numpy() for s in SIDES}
+        else:
+            with np.load(opt.radii) as f:
+                radii = {s: np.asarray(f['radii_' + s], np.float32) for s in SIDES}
+        lr['offset'] = opt.lr if opt.lr_offset is None else opt.lr_offset
+        weights.update(w_off=opt.w_offset, w_off_init=opt.w_offset_init, **({} if opt.w_col is None else {'w_col': opt.w_col}))
     t0 = time.perf_counter()
-    res = fit_targets(tables, targets, opt.iters, lr, weights, opt.bs, opt.cam_scale, start=opt.start, seq_len=seq_len, smooth=smooth,
-                      share_betas=not opt.per_frame_shape)
+    if opt.pair:
+        res, extra = fit_pair_targets(tables, targets, radii, offset, offset_conf, opt.iters, lr, weights, opt.bs, opt.cam_scale, start=opt.start)
+    else:
+        res = fit_targets(tables, targets, opt.iters, lr, weights, opt.bs, opt.cam_scale, start=opt.start, seq_len=seq_len, smooth=smooth,
+                          share_betas=not opt.per_frame_shape)
     torch.cuda.synchronize()
     sec = time.perf_counter() - t0
-    np.savez(opt.out, **{'%s_%s' % (k, s): v for s, d in res.items() for k, v in d.items()})
+    np.savez(opt.out, **{'%s_%s' % (k, s): v for s, d in res.items() for k, v in d.items()}, **extra)
     n = sum(d['para'].shape[0] for d in res.values())
     for s, d in res.items():
         with np.errstate(invalid='ignore'):
             print('%s: %d hands, mean squared residual (verts, joints, joint_uv) %s -> %s, %d with a status' % (
                 s, d['para'].shape[0], d['mse_before'].mean(0).tolist(), d['mse_after'].mean(0).tolist(), int((d['status'] != 0).sum())))
+    if opt.pair:
+        c = extra['collision']
+        print('pairs: largest capsule overlap %.2f -> %.2f mm, %d with a pair status' % (c[:, 1].max() * 1e3, c[:, 3].max() * 1e3, int((extra['pair_status'] != 0).sum())))
     print('%d hands in %.2f s' % (n, sec))
     return n
 

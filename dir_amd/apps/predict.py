@@ -52,6 +52,14 @@ reports a non-finite input or step, keeps the network's values ("refined_hands")
 --smooth filters the refined values.  The defaults are NOT tuned on real keypoints; Adam's steps are lr-sized whatever the residual, so
 keypoints the network already meets to a fraction of a pixel come back jittered at that scale.  Without --keypoints nothing changes.
 
+--separate [--separate_iters 30 --separate_weight 1e4 --separate_prior 1e-2]: after the forward (and after the --keypoints refinement) the two hands of
+every prediction go through the pair fit (dir_mano_fit_pair, utils/mano_fit.py fit_mano_pair) with three terms only: the pull to the prediction's own
+parameters, the pull to its own offset (0.15 x pd_offset, the right root minus the left) and a capsule-per-bone collision term; the betas are frozen.
+A prediction whose capsules overlap and whose fit reports nothing comes back pushed apart ("separated": true); every other one keeps its values bit
+for bit.  Records gain "separated", "collision": {"before": {"mean_sq_overlap", "max_overlap"}, "after": {...}} (metres) and "unseparated" (left,
+right, offset as they were).  --track and --smooth go on from the separated values.  The radii (capsule_radii of the checkpoint's tables) and the
+weights are NOT tuned: this tree has no real MANO tables.  Without --separate nothing changes.
+
 Output per image, <out>/<stem>.json (in --track with sub-directories <out>/<sequence>/<stem>.json):
   image, width, height   the file and its size
   box                    the tight box the crop was made from (null for a frame whose crop was tracked or held)
@@ -179,7 +187,7 @@ class Tracker(object):
     refined one (tracking, smoothing and drawing go on from it), `unrefined` the network's own and `refined_hands` bool [B,2] which hands the
     fit replaced."""
 
-    def __init__(self, eng, ratio=0.8, stage=2, size=SIZE, track=True, antialias=False, smooth=None, smooth_box=None, refine=None):
+    def __init__(self, eng, ratio=0.8, stage=2, size=SIZE, track=True, antialias=False, smooth=None, smooth_box=None, refine=None, separate=None):
         self.eng, self.ratio, self.stage, self.size, self.track = eng, float(ratio), int(stage), int(size), bool(track)
         self.antialias = bool(antialias)
         self.M = self.valid = self.tracked = self.area = None
@@ -195,6 +203,8 @@ class Tracker(object):
             raise ValueError("Tracker: shape_frames needs smooth['space'] = 'para'")
         self.refine = None if refine is None else dict(refine)
         self.unrefined = self.refined_hands = None
+        self.separate = None if separate is None else dict(separate)
+        self.unseparated = self.separated = self.collision = None
 
     def _stage_tables(self):
         e = self.eng
@@ -230,6 +240,35 @@ class Tracker(object):
         self.refined_hands = torch.stack(taken, 1)
         return new
 
+    def _separate(self, o):
+        """the stage dict with the pairs whose capsules overlap pushed apart by the pair fit: the pull to the prediction's own parameters (w_init) and to
+        its own offset (w_off_init) against the collision term (w_col), betas frozen"""
+        import torch
+
+        from .. import _capi
+        from ..utils import mano_fit as MF
+        from ..utils.penetration import OFFSET_UNIT
+        sp, B = self.separate, o['pd_mano_para_left'].shape[0]
+        o0 = (OFFSET_UNIT * _capi.f32c(o['pd_offset']).reshape(B, 3)).contiguous()
+        lr, w_col = float(sp.get('lr', 0.005)), float(sp.get('weight', 1e4))
+        res = MF.fit_mano_pair(list(self._stage_tables()), [o['pd_mano_para_left'], o['pd_mano_para_right']], o0, radii=sp['radii'], iters=int(sp.get('iters', 30)),
+                               lr={'root': lr, 'pca': lr, 'betas': 0.0, 'cam': lr, 'offset': lr},
+                               weights={'w_init': float(sp.get('prior', 1e-2)), 'w_off_init': float(sp.get('offset_prior', 1.0)), 'w_col': w_col})
+        take = (res.pair_status == 0) & ((res.status[0] & 6) == 0) & ((res.status[1] & 6) == 0) & (res.collision[:, 1] > 0) & (self.valid > 0)
+        if not w_col > 0:
+            take = torch.zeros_like(take)                                  # nothing pushes: every pair keeps the network's values
+        new = dict(o)
+        for h, s in enumerate(SIDES):
+            para = torch.where(take[:, None], res.para[h], o['pd_mano_para_' + s])
+            new['pd_mano_para_' + s], new['pd_proj_' + s] = para, para[:, 61:64]
+            for k, r in (('pd_mesh_xyz_', res.verts[h]), ('pd_joint_xyz_', res.joints[h]), ('pd_joint_uv_', res.joint_uv[h])):
+                new[k + s] = torch.where(take[:, None, None], r.to(o[k + s].dtype), o[k + s])
+        off = (res.offset / OFFSET_UNIT).reshape(o['pd_offset'].shape).to(o['pd_offset'].dtype)
+        new['pd_offset'] = torch.where(take.reshape([B] + [1] * (off.dim() - 1)), off, o['pd_offset'])
+        self.separated = take
+        self.collision = torch.where(take[:, None], res.collision, torch.cat([res.collision[:, :2], res.collision[:, :2]], 1))
+        return new
+
     def drawn(self, outs):
         """the stage dict to draw: the smoothed prediction in the current crop, or the stage itself"""
         return self.smoother.crop_stage() if self.smoother is not None else outs[self.stage]
@@ -260,14 +299,18 @@ class Tracker(object):
         else:
             crops, status = CR.crop_frames(batch, self.M, self.valid, self.size, return_status=True)
         self.valid = self.valid * (status == 0).to(torch.int32)            # a crop the kernel refused is black: the image is not valid
-        if self.refine is None and self.smooth_space == 'para':
+        if self.refine is None and self.separate is None and self.smooth_space == 'para':
             outs = self.eng.forward(crops, want_proj_feat=False, want_para=True)
-        elif self.refine is None:
+        elif self.refine is None and self.separate is None:
             outs = self.eng.forward(crops, want_proj_feat=False)
         else:
             outs = list(self.eng.forward(crops, want_proj_feat=False, want_para=True))
-            self.unrefined = outs[self.stage]
-            outs[self.stage] = self._refine(outs[self.stage], keypoints)
+            if self.refine is not None:
+                self.unrefined = outs[self.stage]
+                outs[self.stage] = self._refine(outs[self.stage], keypoints)
+            if self.separate is not None:
+                self.unseparated = outs[self.stage]
+                outs[self.stage] = self._separate(outs[self.stage])
         if self.track:
             M_next, ok = CR.crop_matrices_from_meshes(outs[self.stage], self.M, self.ratio, self.size)
             if self.smooth_box is not None:
@@ -311,6 +354,13 @@ def _records(paths, batch, boxes_used, tr, outs, stage, keep_stage):
         if keep_stage:
             for k in ('pd_mesh_xyz_left', 'pd_mesh_xyz_right', 'pd_proj_left', 'pd_proj_right', 'pd_joint_uv_left', 'pd_joint_uv_right'):
                 t['u_' + k] = un[k].float()
+    us = tr.unseparated if tr.separate is not None else None
+    if us is not None:
+        t['separated'], t['collision'], t['p_offset'] = tr.separated, tr.collision, us['pd_offset'].float()
+        for s in SIDES:
+            t['p_px_' + s] = CR.to_frame_pixels(us['pd_joint_uv_' + s].float(), M, tr.size)
+            t['p_xyz_' + s] = us['pd_joint_xyz_' + s].float()
+            t['p_sc_' + s], t['p_tr_' + s] = CR.frame_camera(us['pd_proj_' + s].float(), M, tr.size)
     fr = tr.smoothed if tr.smooth is not None else None
     if fr is not None:
         t['s_offset'] = fr['offset']
@@ -343,6 +393,13 @@ def _records(paths, batch, boxes_used, tr, outs, stage, keep_stage):
                                   'camera_px': {'scale': num(float(h['u_sc_' + s][j])), 'trans': num(h['u_tr_' + s][j].tolist())}} for s in SIDES}
             r['refined'] = True
             r['refined_hands'] = {s: bool(h['refined_hands'][j][i]) for i, s in enumerate(SIDES)}
+        if us is not None:
+            r['unseparated'] = {s: {'joints_px': num(h['p_px_' + s][j].tolist()), 'joints_xyz': num(h['p_xyz_' + s][j].tolist()),
+                                    'camera_px': {'scale': num(float(h['p_sc_' + s][j])), 'trans': num(h['p_tr_' + s][j].tolist())}} for s in SIDES}
+            r['unseparated']['offset'] = num(h['p_offset'][j].reshape(-1).tolist())
+            r['separated'] = bool(h['separated'][j])
+            c = [float(x) for x in h['collision'][j]]
+            r['collision'] = {'before': {'mean_sq_overlap': num(c[0]), 'max_overlap': num(c[1])}, 'after': {'mean_sq_overlap': num(c[2]), 'max_overlap': num(c[3])}}
         if fr is not None:                                                # the fields above are today's: they move to "raw"
             r['raw'] = {k: r[k] for k in SIDES + ('offset',)}
             for s in SIDES:
@@ -390,12 +447,12 @@ def lockstep_groups(seqs, bs):
     return [[[(g0 + i, item) for i, item in st] for st in lockstep(seqs[g0:g0 + bs])] for g0 in range(0, len(seqs), bs)]
 
 
-def _walk(eng, steps, load, names, box_of, ratio, stage, track, keep_stage, antialias=False, smooth=None, smooth_box=None, refine=None, kp_of=None):
+def _walk(eng, steps, load, names, box_of, ratio, stage, track, keep_stage, antialias=False, smooth=None, smooth_box=None, refine=None, kp_of=None, separate=None):
     """the one loop: per step FrameBatch -> Tracker.step -> records.  load(k) -> the decoded frames of step k; box_of(entry, h, w) -> the
     box of a step entry; kp_of(step index, entry) -> its keypoints entry or None (with refine).  Yields (entries, records, crops, outs, tracker)
     with the device tensors of that step."""
     from ..utils import crop as CR
-    tr = Tracker(eng, ratio, stage, track=track, antialias=antialias, smooth=smooth, smooth_box=smooth_box, refine=refine)
+    tr = Tracker(eng, ratio, stage, track=track, antialias=antialias, smooth=smooth, smooth_box=smooth_box, refine=refine, separate=separate)
     for k, st in enumerate(steps):
         batch = CR.FrameBatch(load(k))
         used = [box_of(e, h, w) for e, (h, w) in zip(st, batch.sizes)] if (not track or k == 0) else None
@@ -453,7 +510,7 @@ def flicker_summary(jitters):
 
 
 def predict(eng, frames, boxes=None, ratio=0.8, stage=2, bs=32, track=False, keep_stage=False, keep_crops=False, antialias=False, smooth=None,
-            smooth_box=None, return_jitter=False, keypoints=None, refine_iters=50, refine_lr=0.01, refine_prior=1e-3):
+            smooth_box=None, return_jitter=False, keypoints=None, refine_iters=50, refine_lr=0.01, refine_prior=1e-3, separate=None):
     """The loop behind the command, on decoded frames.
 
     frames: without `track` a list of uint8 BGR arrays [H,W,3] of any sizes, taken `bs` at a time; with `track` a list of sequences (each
@@ -470,7 +527,10 @@ def predict(eng, frames, boxes=None, ratio=0.8, stage=2, bs=32, track=False, kee
     return_jitter -> (records, [sequence_jitter per sequence]).
     keypoints: one {"left": [[x, y, conf] x 21], "right": ...} or None per image (with `track` one such list per sequence), frame pixels: the
     stage is refined against them (the module docstring's --keypoints; refine_iters, refine_lr, refine_prior); every record then has
-    'unrefined', 'refined' and 'refined_hands', and keep_stage adds 'stage_unrefined'.  None: nothing changes."""
+    'unrefined', 'refined' and 'refined_hands', and keep_stage adds 'stage_unrefined'.  None: nothing changes.
+    separate: a dict with 'radii' (two [20] GPU tensors, utils.mano_fit.capsule_radii) and optionally iters, weight, prior, offset_prior, lr: after the
+    forward (and the refinement) every prediction goes through the pair fit (the module docstring's --separate); every record then has 'separated',
+    'collision' and 'unseparated'.  None: nothing changes."""
     refine = None if keypoints is None else {'iters': refine_iters, 'lr': refine_lr, 'prior': refine_prior}
 
     def kp_of(k, e):
@@ -493,7 +553,7 @@ def predict(eng, frames, boxes=None, ratio=0.8, stage=2, bs=32, track=False, kee
     for steps in groups:
         tr = None
         for st, recs, crops, outs, tr in _walk(eng, steps, lambda k: [f for _, f in steps[k]], lambda e: str(e[0]), box_of, ratio, stage, track,
-                                                keep_stage, antialias, smooth, smooth_box, refine, kp_of):
+                                                keep_stage, antialias, smooth, smooth_box, refine, kp_of, separate):
             ch = crops.cpu().numpy() if keep_crops else None
             for j, ((i, _), r) in enumerate(zip(st, recs)):
                 if keep_crops:
@@ -509,12 +569,13 @@ def predict(eng, frames, boxes=None, ratio=0.8, stage=2, bs=32, track=False, kee
 
 
 def run(eng, sequences, out_dir, boxes=None, ratio=0.8, stage=2, bs=32, track=False, workers=8, pictures=False, joints=False, obj=False,
-        renderer=None, faces=None, antialias=False, smooth=None, smooth_box=None, jitter_out=None, keypoints=None, refine=None):
+        renderer=None, faces=None, antialias=False, smooth=None, smooth_box=None, jitter_out=None, keypoints=None, refine=None, separate=None):
     """files -> files.  sequences: [[paths]] (one list without `track`).  -> (images, seconds, seconds of them spent waiting for decoded
     frames).  Two steps are decoded ahead of the GPU by at most 16 threads; the files are written by 8 more.  With `track`, more than `bs`
     sequences walk `bs` at a time, so that no batch holds more than `bs` images.  smooth / smooth_box: Tracker's; with smooth the pictures
     and OBJs show the filtered prediction, every sequence gets a jitter.json, and a list given as jitter_out receives their contents.
-    keypoints: the --keypoints object (keypoints_for's keys) with refine = {'iters', 'lr', 'prior'}: every stage is refined against them."""
+    keypoints: the --keypoints object (keypoints_for's keys) with refine = {'iters', 'lr', 'prior'}: every stage is refined against them.
+    separate: predict()'s."""
     from concurrent.futures import ThreadPoolExecutor
 
     from ..utils import vis_utils as V
@@ -548,7 +609,7 @@ def run(eng, sequences, out_dir, boxes=None, ratio=0.8, stage=2, bs=32, track=Fa
             tr = None
             for st, recs, crops, outs, tr in _walk(eng, steps, load, lambda e: e[1], lambda e, h, w: box_for(boxes, e[1], h, w), ratio, stage, track,
                                                     False, antialias, smooth, smooth_box, (refine or {}) if keypoints is not None else None,
-                                                    lambda k, e: keypoints_for(keypoints, e[1])):
+                                                    lambda k, e: keypoints_for(keypoints, e[1]), separate):
                 shown = tr.drawn(outs) if pictures or obj else None
                 if pictures:
                     over = V.overlay_predictions(shown, crops, renderer)
@@ -615,9 +676,18 @@ def main(argv=None):
     ap.add_argument('--refine_iters', type=int, default=None, help='with --keypoints: Adam steps of the refinement (default 50; not tuned on real keypoints)')
     ap.add_argument('--refine_lr', type=float, default=None, help='with --keypoints: their learning rate (default 0.01)')
     ap.add_argument('--refine_prior', type=float, default=None, help="with --keypoints: the weight of the pull towards the network's own parameters (default 1e-3)")
+    ap.add_argument('--separate', action='store_true', help='push interpenetrating hands apart: the pair fit with a capsule-per-bone collision term after the forward')
+    ap.add_argument('--separate_iters', type=int, default=None, help='with --separate: Adam steps (default 30; not tuned)')
+    ap.add_argument('--separate_weight', type=float, default=None, help='with --separate: the weight of the collision term (default 1e4; 0: nothing moves)')
+    ap.add_argument('--separate_prior', type=float, default=None, help="with --separate: the weight of the pull towards the prediction's own parameters (default 1e-2)")
     opt = ap.parse_args(argv)
     if opt.bs < 1:
         ap.error('--bs must be at least 1')
+    sp = {k: getattr(opt, 'separate_' + k) for k in ('iters', 'weight', 'prior') if getattr(opt, 'separate_' + k) is not None}
+    if sp and not opt.separate:
+        ap.error('--separate_iters, --separate_weight and --separate_prior need --separate')
+    if min(sp.values(), default=0) < 0:
+        ap.error('--separate_iters, --separate_weight and --separate_prior must not be negative')
     params = {k: getattr(opt, k) for k in ('fps', 'min_cutoff', 'beta', 'd_cutoff') if getattr(opt, k) is not None}
     if (opt.smooth or opt.smooth_box or params) and not opt.track:
         ap.error('--smooth, --smooth_box, --fps, --min_cutoff, --beta and --d_cutoff need --track')
@@ -656,12 +726,17 @@ def main(argv=None):
         if opt.pictures:
             renderer = V.mano_two_hands_shaded_renderer(right_faces=mano['right'].get_faces(), dense_color=np.zeros((V.NV_HAND, 3)), img_size=SIZE,
                                                         device=eng.device)
+    separate = None
+    if opt.separate:
+        from ..utils import mano_fit as MF
+        from .fit_mano import layer_buffers
+        separate = dict(sp, radii=[MF.capsule_radii(layer_buffers(state, s)).to(eng.device) for s in SIDES])
     jitters = []
     smooth_arg = (params or True) if opt.smooth else None
     if opt.smooth and opt.smooth_space == 'para':
         smooth_arg = dict(params, space='para', **({} if opt.shape_frames is None else {'shape_frames': opt.shape_frames}))
     n, sec, wait = run(eng, sequences, opt.out, boxes, opt.ratio, opt.stage, opt.bs, opt.track, opt.workers, opt.pictures, opt.joints, opt.obj,
-                       renderer, faces, opt.antialias, smooth_arg, (params or True) if opt.smooth_box else None, jitters, keypoints, rp)
+                       renderer, faces, opt.antialias, smooth_arg, (params or True) if opt.smooth_box else None, jitters, keypoints, rp, separate)
     print('waited %.2f s of them for decoded frames' % wait)
     if opt.smooth:
         mm, px = jitter_summary(jitters)

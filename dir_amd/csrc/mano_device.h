@@ -1,6 +1,7 @@
 // The MANO layer on the device, in ONE place: manopth/manopth/manolayer.py:110-270 (+ rodrigues_layer.py:15-54, rot6d.py:26-60,
-// tensutils.py:6-42) of the reference and its reverse.  Six kernels call it: mano_forward_kernel (mano.hip), mano_backward_kernel
-// (mano_bwd.hip), mano_fit_kernel (mano_fit.hip), mano_fit_seq_kernel (mano_fit_seq.hip), mano_fit_start_kernel (mano_fit_start.hip) and mano_para_smooth_kernel (para_smooth.hip).  That mano_fit's iters = 0 and the
+// tensutils.py:6-42) of the reference and its reverse.  Seven kernels call it: mano_forward_kernel (mano.hip), mano_backward_kernel
+// (mano_bwd.hip), mano_fit_kernel (mano_fit.hip), mano_fit_seq_kernel (mano_fit_seq.hip), mano_fit_pair_kernel (mano_fit_pair.hip: two hands per 512-thread
+// workgroup, the thread index taken modulo 256), mano_fit_start_kernel (mano_fit_start.hip) and mano_para_smooth_kernel (para_smooth.hip).  That mano_fit's iters = 0 and the
 // smoother's first usable frame give dir_mano_forward's bits, and that the backward differentiates what the forward computes, holds
 // because they run the same functions.
 //

@@ -2,6 +2,8 @@
 // include/dir_hip.h, "MANO fitting"), the mean squared residuals, and the priors' gradients with one Adam step of one component (steps 4 and 5).
 // mano_fit_kernel (mano_fit.hip: the loop inside one launch) and mano_fit_seq_kernel (mano_fit_seq.hip: one launch per iteration, frames coupled
 // in time) call them, which is why a sequence fitted with no temporal weight and a shape per frame gives dir_mano_fit's bits.
+// mano_fit_pair_kernel (mano_fit_pair.hip: both hands of a pair in one workgroup) calls them too and adds the capsule term at the end of this file; with no
+// capsule pair active it gives dir_mano_fit's bits for the same reason.
 //
 // As mano_device.h: everything is __forceinline__, a function holds NO barrier (the kernels keep every __syncthreads()), fp32 throughout, every sum
 // in a fixed order.
@@ -94,6 +96,61 @@ __device__ __forceinline__ bool adam(float g, float lr, float b1, float b2, floa
 }
 
 __device__ __forceinline__ int group_of(int i) { return i < 6 ? 0 : i < 51 ? 1 : i < 61 ? 2 : 3; }
+
+// ---- the capsule term of dir_mano_fit_pair (include/dir_hip.h, "MANO fitting: two hands together")
+constexpr float kSegEps = 1e-12f;        // m^2: a segment shorter than 1 um is a point
+constexpr float kMinDist = 1e-6f;        // m: below it two segments cross and the pair has no direction
+
+__device__ __forceinline__ float clamp01(float x) { return x < 0.f ? 0.f : x > 1.f ? 1.f : x; }       // NaN stays NaN
+
+// Ericson's closest points of the segments (A, B) and (C, D), the header's order of clamps and branches: the clamped parameters s, t, the
+// distance d and n = (c1 - c2) / d.  No FMA contraction.
+__device__ __forceinline__ void segment_closest(const float (&A)[3], const float (&B)[3], const float (&C)[3], const float (&D)[3], float& s, float& t,
+                                                float (&n)[3], float& d) {
+#pragma clang fp contract(off)
+    const float d1[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]}, d2[3] = {D[0] - C[0], D[1] - C[1], D[2] - C[2]};
+    const float r[3] = {A[0] - C[0], A[1] - C[1], A[2] - C[2]};
+    const float a = d1[0] * d1[0] + d1[1] * d1[1] + d1[2] * d1[2], e = d2[0] * d2[0] + d2[1] * d2[1] + d2[2] * d2[2];
+    const float f = d2[0] * r[0] + d2[1] * r[1] + d2[2] * r[2];
+    if (a <= kSegEps && e <= kSegEps) {
+        s = 0.f; t = 0.f;
+    } else if (a <= kSegEps) {
+        s = 0.f; t = clamp01(f / e);
+    } else {
+        const float c = d1[0] * r[0] + d1[1] * r[1] + d1[2] * r[2];
+        if (e <= kSegEps) {
+            t = 0.f; s = clamp01(-c / a);
+        } else {
+            const float b = d1[0] * d2[0] + d1[1] * d2[1] + d1[2] * d2[2], den = a * e - b * b;
+            s = den != 0.f ? clamp01((b * f - c * e) / den) : 0.f;
+            t = (b * s + f) / e;
+            if (t < 0.f) { t = 0.f; s = clamp01(-c / a); }
+            else if (t > 1.f) { t = 1.f; s = clamp01((b - c) / a); }
+        }
+    }
+    const float w[3] = {(A[0] + s * d1[0]) - (C[0] + t * d2[0]), (A[1] + s * d1[1]) - (C[1] + t * d2[1]), (A[2] + s * d1[2]) - (C[2] + t * d2[2])};
+    d = sqrtf(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+    n[0] = w[0] / d; n[1] = w[1] / d; n[2] = w[2] / d;
+}
+
+// one (left bone, right bone) pair: h (0 where the pair is skipped), whether it is active, whether it has no direction, and for an active pair the four
+// endpoint gradients of step 2a
+__device__ __forceinline__ void capsule_pair(const float (&A)[3], const float (&B)[3], const float (&C)[3], const float (&D)[3], float rsum, float k_col,
+                                             float& h, bool& active, bool& nodir, float (&gA)[3], float (&gB)[3], float (&gC)[3], float (&gD)[3]) {
+#pragma clang fp contract(off)
+    float s, t, n[3], d;
+    segment_closest(A, B, C, D, s, t, n, d);
+    h = 0.f; active = false; nodir = false;
+    if (!dir::finite(d)) { nodir = true; return; }
+    const float hh = rsum - d;
+    if (!(hh > 0.f)) return;
+    h = hh;
+    if (d < kMinDist) { nodir = true; return; }
+    active = true;
+    const float u = k_col * hh, ua = u * (1.f - s), ub = u * s, uc = u * (1.f - t), ud = u * t;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { gA[c] = -(ua * n[c]); gB[c] = -(ub * n[c]); gC[c] = uc * n[c]; gD[c] = ud * n[c]; }
+}
 
 }  // namespace fit
 }  // namespace mano

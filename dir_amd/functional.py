@@ -370,6 +370,64 @@ def mano_fit(tables_lr, init_lr, verts=None, joints=None, joints_conf=None, join
     return res
 
 
+MANO_FIT_PAIR_WEIGHTS = ('w_col', 'w_off', 'w_off_init')
+
+
+def mano_fit_pair(tables_lr, init_lr, offset0, radii, verts=None, joints=None, joints_conf=None, joint_uv=None, uv_conf=None, iters=200, lr=(0.1, 0.1, 0.1, 0.1),
+                  lr_offset=0.0, weights=None, pair_weights=None, offset_target=None, offset_conf=None, offset_anchor=None, betas=(0.9, 0.999), eps=1e-8,
+                  anchor=None, state=None, offset_state=None, outputs=True, para_out=None, offset_out=None):
+    """dir_mano_fit_pair (include/dir_hip.h, "MANO fitting: two hands together").  The per-hand arguments are mano_fit's with two hands (left slot, right
+    slot); offset0 [B,3]; radii: two float32 [20] GPU tensors; pair_weights: dict over MANO_FIT_PAIR_WEIGHTS (missing = 0); offset_target [B,3] /
+    offset_conf [B] / offset_anchor [B,3] / offset_state [B, MANO_FIT_PAIR_STATE] (updated in place) / offset_out [B,3] (may be offset0): optional.
+    -> (list per hand of mano_fit's dicts, dict offset [B,3], col [B,4], pair_status [B])."""
+    import ctypes as C
+    assert len(init_lr) == 2 and len(tables_lr) == 2 and len(radii) == 2
+    B, dev = init_lr[0].shape[0], init_lr[0].device
+
+    def per_hand(ts, shape, what):
+        ts = [None] * 2 if ts is None else list(ts)
+        assert len(ts) == 2
+        for t in ts:
+            if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape and t.device == dev):
+                raise _capi.DirHipError('mano_fit_pair: %s must be a contiguous float32 %s tensor on %s' % (what, list(shape), dev))
+        _capi.require_cuda(*ts)
+        return ts
+    one = lambda t, shape, what: per_hand([t, None], shape, what)[0]  # noqa: E731
+    init = per_hand(init_lr, (B, 64), 'init')
+    tv, tj, cj = per_hand(verts, (B, 778, 3), 'verts'), per_hand(joints, (B, 21, 3), 'joints'), per_hand(joints_conf, (B, 21), 'joints_conf')
+    tu, cu = per_hand(joint_uv, (B, 21, 2), 'joint_uv'), per_hand(uv_conf, (B, 21), 'uv_conf')
+    an, st, po = per_hand(anchor, (B, 64), 'anchor'), per_hand(state, (B, _capi.MANO_FIT_STATE), 'state'), per_hand(para_out, (B, 64), 'para_out')
+    rad = per_hand(radii, (20,), 'radii')
+    o0, ot, oc, oa = one(offset0, (B, 3), 'offset0'), one(offset_target, (B, 3), 'offset_target'), one(offset_conf, (B,), 'offset_conf'), one(offset_anchor, (B, 3), 'offset_anchor')
+    ost, oo = one(offset_state, (B, _capi.MANO_FIT_PAIR_STATE), 'offset_state'), one(offset_out, (B, 3), 'offset_out')
+    if o0 is None or rad[0] is None or rad[1] is None:
+        raise _capi.DirHipError('mano_fit_pair: offset0 and both radii are required')
+    w, pw = dict(weights or {}), dict(pair_weights or {})
+    if set(w) - set(MANO_FIT_WEIGHTS) or set(pw) - set(MANO_FIT_PAIR_WEIGHTS):
+        raise ValueError('mano_fit_pair: unknown weights %s' % sorted((set(w) - set(MANO_FIT_WEIGHTS)) | (set(pw) - set(MANO_FIT_PAIR_WEIGHTS))))
+    opts = _capi.ManoFitOpts(*[float(w.get(k, 0.0)) for k in MANO_FIT_WEIGHTS], (C.c_float * 4)(*[float(v) for v in lr]), float(betas[0]), float(betas[1]),
+                             float(eps), int(iters))
+    popts = _capi.ManoFitPairOpts(*[float(pw.get(k, 0.0)) for k in MANO_FIT_PAIR_WEIGHTS], float(lr_offset))
+    res, hs = [], []
+    P = _capi.ptr
+    for h in range(2):
+        r = {'para': po[h] if po[h] is not None else torch.empty(B, 64, device=dev), 'mse': torch.empty(B, 6, device=dev),
+             'status': torch.empty(B, dtype=torch.int32, device=dev)}
+        if outputs:
+            r.update(verts=torch.empty(B, 778, 3, device=dev), joints=torch.empty(B, 21, 3, device=dev), joint_uv=torch.empty(B, 21, 2, device=dev))
+        hs.append(_capi.ManoFitHand(init[h].data_ptr(), P(an[h]), r['para'].data_ptr(), P(tv[h]), P(tj[h]), P(cj[h]), P(tu[h]), P(cu[h]),
+                                    P(r.get('verts')), P(r.get('joints')), P(r.get('joint_uv')), r['mse'].data_ptr(), r['status'].data_ptr(), P(st[h])))
+        res.append(r)
+    pr = {'offset': oo if oo is not None else torch.empty(B, 3, device=dev), 'col': torch.empty(B, 4, device=dev),
+          'pair_status': torch.empty(B, dtype=torch.int32, device=dev)}
+    pargs = _capi.ManoFitPairArgs(o0.data_ptr(), P(ot), P(oc), P(oa), (C.c_void_p * 2)(rad[0].data_ptr(), rad[1].data_ptr()), pr['offset'].data_ptr(),
+                                  pr['col'].data_ptr(), pr['pair_status'].data_ptr(), P(ost))
+    with torch.cuda.device(dev):
+        _capi.check(_capi.lib().dir_mano_fit_pair((_capi.ManoTables * 2)(*tables_lr), (_capi.ManoFitHand * 2)(*hs), C.byref(opts), C.byref(pargs), C.byref(popts),
+                                                  B, _capi.stream_ptr()), 'dir_mano_fit_pair')
+    return res, pr
+
+
 def mano_fit_start(tables_lr, init_lr, verts=None, joints=None, joints_conf=None, joint_uv=None, uv_conf=None, w_verts=0.0, w_joints=0.0, root=True, cam=True,
                    search=True, para_out=None):
     """dir_mano_fit_start (include/dir_hip.h, "MANO fitting: closed-form start").  Arguments as mano_fit's (lists with one tensor or None per hand;

@@ -23,6 +23,12 @@ is no longer out of Adam's reach, and cam_scale need not be guessed.
 Whole sequences (include/dir_hip.h, "MANO fitting: sequences"; csrc/mano_fit_seq.hip): the N frames of S sequences laid end to end are ONE optimisation --
 one shape per (sequence, hand), a pose and a camera per frame, neighbouring frames coupled in time -- so the betas do not change from frame to frame and a
 frame without keypoints is filled from its neighbours.  One launch per iteration (two with the shared shape), all enqueued by one library call.
+
+    res = fit_mano_pair([left, right], [init_l, init_r], offset0, radii=[capsule_radii(left), capsule_radii(right)], joints=[jl, jr], weights={'w_joints': 1e4, 'w_col': 1e4})
+    res.para / verts / ... lists of two as fit_mano's pair form, res.offset [B,3], res.collision [B,4], res.pair_status [B]
+
+Two hands together (include/dir_hip.h, "MANO fitting: two hands together"; csrc/mano_fit_pair.hip): the two hands of a pair and the offset between their centre
+joints are ONE optimisation, with a capsule per bone that keeps the hands from passing through each other.  One launch, one 512-thread workgroup per pair.
 """
 import collections
 
@@ -206,3 +212,97 @@ def fit_mano_sequence(layer_or_tables, init, seq_lengths, verts=None, joints=Non
         return rs[0]
     out = SeqFitResult(*[list(f) for f in zip(*rs)])
     return out._replace(state=state)
+
+
+# ---- two hands together: dir_mano_fit_pair (csrc/mano_fit_pair.hip; include/dir_hip.h, "MANO fitting: two hands together")
+DEFAULT_PAIR_WEIGHTS = {'w_col': 1e4, 'w_off': 0.0, 'w_off_init': 0.0}      # NOT tuned: this tree has no real MANO tables
+PAIR_STATUS_HAND_PASSED, PAIR_STATUS_OFFSET_PASSED, PAIR_STATUS_OFFSET_FROZEN, PAIR_STATUS_NO_DIRECTION = 1, 2, 4, 8
+BONE_PARENT = (0, 1, 2, 3, 0, 5, 6, 7, 0, 9, 10, 11, 0, 13, 14, 15, 0, 17, 18, 19)           # bone k joins joints BONE_PARENT[k] and k + 1
+_REORDER = (0, 13, 14, 15, 16, 1, 2, 3, 17, 4, 5, 6, 18, 10, 11, 12, 19, 7, 8, 9, 20)       # output joint -> chain joint (0..15) or fingertip (16..20)
+_TIPS = {'right': (745, 317, 444, 556, 673), 'left': (745, 317, 445, 556, 673)}
+PairFitResult = collections.namedtuple('PairFitResult', FitResult._fields + ('offset', 'collision', 'pair_status', 'offset_state'))
+
+
+def new_offset_state(B, device='cuda'):
+    """a fresh Adam state of the offset [B, 12]: m | v | b1^t | b2^t | t | 0 0 0 -- all zeros"""
+    return torch.zeros(B, _capi.MANO_FIT_PAIR_STATE, device=device)
+
+
+def capsule_radii(layer_or_tables, q=0.5):
+    """One radius per bone [20] (float32, on the tables' device) for fit_mano_pair's capsules, from the template pose: bone k joins output joints
+    BONE_PARENT[k] and k + 1; its radius is the q-quantile of the distances to that segment over the vertices whose largest skinning weight belongs to the
+    bone's parent joint (the five fingertip bones have a fingertip as their child: their vertices are the last chain joint's, the child's side).  A bone
+    without such a vertex gets 0.  Plain torch, done once.  layer_or_tables: a ManoLayer, or a mapping with th_v_template [778,3], th_weights [778,16],
+    th_J_regressor [16,778] and 'side' (a _capi.ManoTables holds bare pointers and cannot be read here).  UNTUNED: q, like every default weight of
+    fit_mano_pair, has not been set on real MANO tables -- this tree has none."""
+    get = (lambda k: layer_or_tables[k]) if isinstance(layer_or_tables, dict) else (lambda k: getattr(layer_or_tables, k))
+    v = get('th_v_template').reshape(778, 3).double()
+    w = get('th_weights').reshape(778, 16).double()
+    jr = get('th_J_regressor').reshape(16, 778).double()
+    side = get('side')
+    src = torch.cat([jr @ v, v[list(_TIPS[side])]], 0)[list(_REORDER)]                 # the 21 output joints at the template pose
+    owner = w.argmax(1)                                                               # chain joint of each vertex
+    out = torch.zeros(20, dtype=torch.float64, device=v.device)
+    for k in range(20):
+        pa = BONE_PARENT[k]
+        chain = _REORDER[pa]                                                          # always < 16: no bone starts at a fingertip
+        pts = v[owner == chain]
+        if pts.shape[0] == 0:
+            continue
+        a, b = src[pa], src[k + 1]
+        ab = b - a
+        t = ((pts - a) @ ab / (ab @ ab).clamp(min=1e-30)).clamp(0, 1)
+        out[k] = torch.quantile((pts - (a + t[:, None] * ab)).norm(dim=1), float(q))
+    return out.float().contiguous()
+
+
+def fit_mano_pair(layers_or_tables, init, offset0, *, radii=None, offset_target=None, offset_conf=None, offset_anchor=None, verts=None, joints=None,
+                  joints_conf=None, joint_uv=None, uv_conf=None, iters=200, lr=0.1, weights=None, state=None, anchor=None, start='neutral', outputs=True,
+                  betas=(0.9, 0.999), eps=1e-8):
+    """One launch of dir_mano_fit_pair: both hands of B pairs fitted together with the offset o [B,3] (right centre joint minus left, metres; 0.15 x the
+    network's pd_offset) and a capsule-per-bone collision term between the hands.  layers_or_tables, init and every per-hand target: lists of two (left
+    slot, right slot), as fit_mano's pair form.  radii: two [20] tensors (None: capsule_radii of the two layers, q = 0.5).  lr: a float, or a dict over
+    GROUPS + ('offset',) (a missing group is frozen).  weights: one dict over fit_mano's keys and w_col, w_off, w_off_init (None: DEFAULT_WEIGHTS for the
+    terms whose targets are given, and DEFAULT_PAIR_WEIGHTS).  state: True for fresh ones, or (the list of two hand states, the offset state) of an earlier
+    result.  start: 'neutral', or 'closed' (start_mano per hand first, as fit_mano).  -> PairFitResult: fit_mano's pair result + offset [B,3], collision
+    [B,4] (mean squared overlap and largest overlap in metres at the start, then at the end) and pair_status [B].  Every default (radii quantile, weights, rates) is
+    UNTUNED: this tree has no real MANO tables."""
+    if start not in ('neutral', 'closed'):
+        raise ValueError("fit_mano_pair: start is 'neutral' or 'closed', got %r" % (start,))
+    if len(layers_or_tables) != 2 or len(init) != 2:
+        raise ValueError('fit_mano_pair: takes lists of two')
+    term_w = None if weights is None else {k: v for k, v in weights.items() if k in F.MANO_FIT_WEIGHTS}
+    pair_w = dict(DEFAULT_PAIR_WEIGHTS) if weights is None else {k: v for k, v in weights.items() if k in F.MANO_FIT_PAIR_WEIGHTS}
+    if weights is not None and set(weights) - set(F.MANO_FIT_WEIGHTS) - set(F.MANO_FIT_PAIR_WEIGHTS):
+        raise ValueError('fit_mano_pair: unknown weights %s' % sorted(set(weights) - set(F.MANO_FIT_WEIGHTS) - set(F.MANO_FIT_PAIR_WEIGHTS)))
+    if start == 'closed':
+        init = start_mano(list(layers_or_tables), list(init), verts, joints, joints_conf, joint_uv, uv_conf, term_w).para
+        anchor = init if anchor is None else anchor
+    opt = lambda x: None if x is None else [None if t is None else _capi.f32c(t) for t in x]  # noqa: E731
+    one = lambda t: None if t is None else _capi.f32c(t)  # noqa: E731
+    tabs = [_tables(x) for x in layers_or_tables]
+    p0 = [_capi.f32c(t) for t in init]
+    B, dev = p0[0].shape[0], p0[0].device
+    if radii is None:
+        radii = [capsule_radii(x).to(dev) for x in layers_or_tables]
+    if isinstance(lr, dict):
+        if set(lr) - set(GROUPS) - {'offset'}:
+            raise ValueError("fit_mano_pair: lr groups are %s and 'offset', got %s" % (GROUPS, sorted(lr)))
+        lr4, lr_o = [float(lr.get(g, 0.0)) for g in GROUPS], float(lr.get('offset', 0.0))
+    else:
+        lr4, lr_o = [float(lr)] * 4, float(lr)
+    term_w = _term_weights(term_w, verts, joints, joint_uv)
+    if state is True:
+        state = ([new_state(B, dev), new_state(B, dev)], new_offset_state(B, dev))
+    st, ost = (None, None) if state is None else (list(state[0]), state[1])
+    o0 = _capi.f32c(offset0)
+    if B == 0:
+        e = lambda *s: torch.empty((0,) + s, device=dev)  # noqa: E731
+        ei = torch.empty(0, dtype=torch.int32, device=dev)
+        rs = [FitResult(p.clone(), e(778, 3), e(21, 3), e(21, 2), e(3), e(3), ei.clone(), None if st is None else st[h]) for h, p in enumerate(p0)]
+        return PairFitResult(*[list(f) for f in zip(*rs)], o0.clone(), e(4), ei, ost)
+    res, pr = F.mano_fit_pair(tabs, p0, o0, [_capi.f32c(r) for r in radii], opt(verts), opt(joints), opt(joints_conf), opt(joint_uv), opt(uv_conf), iters, lr4, lr_o,
+                              term_w, pair_w, one(offset_target), one(offset_conf), one(offset_anchor), betas, eps, opt(anchor), st, ost, outputs)
+    rs = [FitResult(r['para'], r.get('verts'), r.get('joints'), r.get('joint_uv'), r['mse'][:, :3], r['mse'][:, 3:], r['status'],
+                    None if st is None else st[h]) for h, r in enumerate(res)]
+    return PairFitResult(*[list(f) for f in zip(*rs)], pr['offset'], pr['col'], pr['pair_status'], ost)

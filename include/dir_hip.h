@@ -29,7 +29,7 @@ extern "C" {
 #define DIR_E_LAUNCH (-2)   /* hipLaunchKernel / HIP runtime error          */
 #define DIR_E_NODEVICE (-3) /* no gfx950 device visible                     */
 
-#define DIR_ABI_VERSION 56
+#define DIR_ABI_VERSION 57
 
 int dir_abi_version(void);
 const char* dir_last_error(void);
@@ -321,6 +321,82 @@ size_t dir_mano_fit_sequence_workspace_bytes(int N, int S, int hands);
 int dir_mano_fit_sequence(const dir_mano_tables* tables_host, const dir_mano_fit_hand* hands_host, const dir_mano_fit_opts* opts_host,
                           const dir_mano_fit_seq_opts* seq_opts_host, const int32_t* seq_start, int S, int N, int hands, int32_t* seq_status,
                           void* work, size_t work_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * MANO fitting: two hands together (ABI 57; csrc/mano_fit_pair.hip; nothing in the reference).  dir_mano_fit fits each hand alone and has no
+ * variable for where the right hand is relative to the left.  dir_mano_fit_pair fits B PAIRS: per pair the two 64-vectors p_L, p_R of
+ * dir_mano_fit (hands_host[0] = left slot, [1] = right slot) and the 3-vector o = the right hand's centre joint minus the left hand's, metres,
+ * camera axes (0.15 * pd_offset of the network).  In the common frame the left joints are X^L_j = J^L_j and the right joints X^R_j = J^R_j + o,
+ * J = dir_mano_fit's centred output joints (the output's bits; the sum with o rounded once).  tests/helpers/mano_pair_fit_ref.py restates the rule.
+ *
+ *   E = E_fit(p_L) + E_fit(p_R)                             dir_mano_fit's E, the same dir_mano_fit_opts for both hands
+ *     + w_off * c_o * |o - o*|^2                             o* = o_target; dropped when o_target is NULL or c_o is not > 0 (o* may then hold NaN)
+ *     + w_off_init * |o - o_a|^2                             o_a = o_anchor, or o0 where it is NULL
+ *     + w_col / 400 * sum_{i<20} sum_{j<20} h_ij^2           h_ij = max(0, (r^L_i + r^R_j) - d_ij)
+ *
+ * Bones: bone k joins joints parent(k) and child(k) = k + 1, parent = {0,1,2,3, 0,5,6,7, 0,9,10,11, 0,13,14,15, 0,17,18,19} (csrc/bone_common.h,
+ * the reference's Joint2BoneFeature).  radii[0] = r^L, radii[1] = r^R: [20] floats on the device.  d_ij = the distance between the segments
+ * (A, B) = (X^L_parent(i), X^L_child(i)) and (C, D) = (X^R_parent(j), X^R_child(j)), by Ericson's closest points of two segments, fp32, every
+ * operation rounded (no FMA contraction), dot products summed x, y, z left to right, clamp(x) = x < 0 ? 0 : x > 1 ? 1 : x:
+ *     d1 = B - A, d2 = D - C, r = A - C, a = d1.d1, e = d2.d2, f = d2.r, eps = 1e-12 (m^2: a segment shorter than 1 um is a point)
+ *     if a <= eps and e <= eps:   s = 0, t = 0
+ *     else if a <= eps:           s = 0, t = clamp(f / e)
+ *     else: c = d1.r
+ *        if e <= eps:             t = 0, s = clamp(-c / a)
+ *        else: b = d1.d2, den = a e - b b
+ *             s = den != 0 ? clamp((b f - c e) / den) : 0          (parallel segments: s = 0)
+ *             t = (b s + f) / e
+ *             if t < 0:           t = 0, s = clamp(-c / a)
+ *             else if t > 1:      t = 1, s = clamp((b - c) / a)
+ *     c1 = A + s d1, c2 = C + t d2, w = c1 - c2, d = sqrt(w.w), n = w / d
+ * A pair with d finite and >= 1e-6 and h > 0 is ACTIVE.  A pair with d not finite contributes nothing; a pair with d < 1e-6 and h > 0 (the segments
+ * cross: no direction) contributes h to the report below and no gradient; both set pair_status bit 3.  Every other pair (h = 0) is skipped.
+ *
+ * One iteration: dir_mano_fit's steps 1-5 for both hands at the same iterate, with these additions, and only while the coupling is on (below):
+ *   2a. (between steps 2 and 3, only with w_col > 0) for every active pair, with u = k_col h, k_col = 2 w_col / 400 formed in double on the host and
+ *       rounded once -- the envelope gradient, s and t held fixed, every product rounded:
+ *         gA = -(u (1 - s)) n     gB = -(u s) n     gC = (u (1 - t)) n     gD = (u t) n     g_pair = gC + gD
+ *       per left bone i: GA_i = sum_j gA, GB_i = sum_j gB, go_i = sum_j g_pair over the active j ascending (from 0.f); per right bone j: GC_j, GD_j over
+ *       the active i ascending.  Then per hand and joint q: gJ_q = gJ_q + (the sum, from 0.f, over the bones k ascending that have an active pair
+ *       of: the parent-end sum where parent(k) = q, the child-end sum where child(k) = q), and the hand's sum of all cotangents (what centre() hands
+ *       to the centre joint) S = S + (the sum over the same bones k ascending of parent-end + child-end).  A bone without an active pair and a
+ *       joint without such a bone are skipped, never added as zero.  g_o = the sum over i ascending of go_i for the bones i with an active pair.
+ *   4a. g_o = g_o + (k_off c_o) (o - o*) where the target is in use, then g_o = g_o + k_oi (o - o_a); k_off = 2 w_off, k_oi = 2 w_off_init.
+ *   5a. step 5 on the three components of o with lr_o and o's own m, v, P1, P2, t (a fifth group).  lr_o == 0 keeps o bit for bit.
+ *
+ * Rows.  The coupling of a pair is ON when neither hand passes through (dir_mano_fit's status bit 1) and o0, o_a, the target in use (c_o included)
+ * and the 40 radii are finite.  Otherwise o passes through (offset_out = o0 bit for bit, its state untouched), no term above the two E_fit exists,
+ * col is 0, and each hand is fitted exactly as dir_mano_fit fits it.  A hand frozen by a non-finite step (status bit 2) stays where it is as an
+ * obstacle while the other hand and o go on.  A non-finite step of o is not taken and freezes o at its last finite value (the collision term stays).
+ * pair_status (int32 per pair, optional): bit 0 a hand passes through: coupling off; bit 1 o0 / o_a / o* / c_o / radii non-finite: coupling off;
+ *   bit 2 o frozen by a non-finite step; bit 3 a pair without direction (or with a non-finite distance) was met at an evaluated iterate.
+ * With w_col = 0, no o_target, w_off_init = 0 and lr_o = 0, and whenever no pair is active, both hands' outputs and states are dir_mano_fit's bits.
+ *
+ * Outputs on top of each hand's dir_mano_fit outputs: offset_out [B,3] (may alias o0); col [B,4] (optional) = (sum_i (sum_j h_ij^2)) / 400 and max h_ij
+ * in metres (i ascending, j ascending inside; max from 0) at the start, then the same two at the returned iterate: with iters = 0 the call is the
+ * measure alone, and the measure does not depend on w_col.  o_state [B, DIR_MANO_FIT_PAIR_STATE] (optional, in and out): m [3] | v [3] | P1 | P2 |
+ * t (the int32's bits) | 0 0 0; it follows the two hands' DIR_MANO_FIT_STATE blocks (hands_host[h].state), which keep dir_mano_fit's layout, so a
+ * hand's state moves between the two entry points.  With all three, iters = a then iters = b equals iters = a + b bit for bit.
+ * One launch, one 512-thread workgroup per pair (threads 0-255 the left slot, 256-511 the right, each through dir_mano_fit's phases), fp32, no
+ * atomics, no workspace, no allocation, no host read; enqueued on `stream`, graph-capture safe; a pair gives the same bits in any slot of any batch. */
+#define DIR_MANO_FIT_PAIR_STATE 12
+typedef struct dir_mano_fit_pair_args {
+    const float* o0;          /* [B,3] start                                               */
+    const float* o_target;    /* o* [B,3] or NULL                                          */
+    const float* o_conf;      /* c_o [B] or NULL (= 1)                                     */
+    const float* o_anchor;    /* o_a [B,3] or NULL = o0                                    */
+    const float* radii[2];    /* r^L, r^R: [20] each                                       */
+    float* offset_out;        /* [B,3] (may alias o0)                                      */
+    float* col;               /* [B,4] or NULL                                             */
+    int32_t* pair_status;     /* [B] or NULL                                               */
+    float* o_state;           /* [B,DIR_MANO_FIT_PAIR_STATE] in and out, or NULL           */
+} dir_mano_fit_pair_args;
+typedef struct dir_mano_fit_pair_opts {
+    float w_col, w_off, w_off_init, lr_o;   /* finite and >= 0 */
+} dir_mano_fit_pair_opts;
+/* tables_host / hands_host: HOST arrays of exactly two entries (left slot, right slot). */
+int dir_mano_fit_pair(const dir_mano_tables* tables_host, const dir_mano_fit_hand* hands_host, const dir_mano_fit_opts* opts_host,
+                      const dir_mano_fit_pair_args* pair_host, const dir_mano_fit_pair_opts* pair_opts_host, int B, void* stream);
 
 /* Backward of RegressorOffset's three Linears (models/dir.py:339-351).  w_left / w_right [64][1408], w_offset [3][2691]: the
  * nn.Linear weights in their own layout; tok [B,42,64] = the STE head output (tokens 0..20 left); prev_* the previous stage's
