@@ -6,8 +6,8 @@
 // pass behind dir_stage_losses_backward.
 //
 // One 256-thread workgroup per (sample, hand).  The forward is recomputed in LDS (pose maths, chain, posed and skinned vertices:
-// cheaper than round-tripping 30 KB of intermediates per (sample, hand) through HBM) by mano_device.h's forward phases, then reversed
-// stage by stage by its backward phases (mano_fit.hip runs the same ones); the projection and the cotangents are this kernel's own:
+// cheaper than round-tripping 30 KB of intermediates per (sample, hand) through HBM) by mano_device.h's forward schedule, then reversed
+// stage by stage by its backward schedule (the three fit kernels run the same two); the projection and the cotangents are this kernel's own:
 //   projection / centring -> joint routing (chain joints, fingertip vertices) -> skinning (g v_posed per vertex; g A'_k as 192
 //   reductions over the 778 vertices) -> A' -> A -> kinematic chain (one thread per finger, root partials combined afterwards)
 //   -> pose blend shapes (135 wave-level dot products over the k-major table) -> Rodrigues-via-quaternion and robust-6D chain
@@ -46,7 +46,7 @@ __global__ __launch_bounds__(BT) void mano_backward_kernel(ManoBwdArgs args) {
 
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
-    // ================================================================ forward (mano_device.h, layer 2)
+    // ================================================================ forward (mano_device.h, layers 2 and 4)
     if (tid < 51) s_pose[tid] = a.pose[(size_t)b * a.pose_stride + tid];
     if (tid >= 64 && tid < 74) s_beta[tid - 64] = a.betas[(size_t)b * a.betas_stride + tid - 64];
     if (tid >= 128 && tid < 131) s_cam[tid - 128] = a.cam ? a.cam[(size_t)b * a.cam_stride + tid - 128] : 0.f;
@@ -55,19 +55,7 @@ __global__ __launch_bounds__(BT) void mano_backward_kernel(ManoBwdArgs args) {
     shape_blend(T, s_beta, s_v, tid);
     if (tid == 64) { int reflect; robust6d(s_pose, L.root, reflect); }
     __syncthreads();
-    joint_rotations(L, s_full, tid);
-    joint_regression(L, T, s_beta, tid);
-    __syncthreads();
-    pose_blend(L, T, s_v, tid);
-    chain(L, tid);
-    __syncthreads();
-    a_primes(L, tid);
-    __syncthreads();
-    skinning(L, T, s_v, s_vert, tid);
-    __syncthreads();
-    joints(L, side, root_palm, s_vert, tid);
-    __syncthreads();
-    centre(L, center, tid);
+    forward_schedule(L, T, side, center, root_palm, s_full, s_beta, s_v, s_vert, tid);
     __syncthreads();
 
     // ================================================================ backward
@@ -104,23 +92,8 @@ __global__ __launch_bounds__(BT) void mano_backward_kernel(ManoBwdArgs args) {
     __syncthreads();
     if (tid < 6) s_sum[tid] = s_red[0][tid] + s_red[1][tid] + s_red[2][tid] + s_red[3][tid];
     __syncthreads();
-    // ---- the layer's backward (mano_device.h, layer 3)
-    centre_bwd(G, center, s_sum, tid);
-    __syncthreads();
-    joints_bwd(G, side, root_palm, s_gv, tid);
-    __syncthreads();
-    skinning_bwd(L, T, s_gv, s_gvp, tid);
-    a_primes_grad(G, T, s_gv, s_v, tid);
-    __syncthreads();
-    a_primes_bwd(G, L, tid);
-    __syncthreads();
-    chain_bwd(G, L, tid);
-    __syncthreads();
-    chain_root_bwd(G, tid);
-    __syncthreads();
-    root_split_bwd(G, tid);
-    pose_blend_bwd<dir::wave_sum>(L, T, s_gvp, tid);
-    __syncthreads();
+    // ---- the layer's backward (mano_device.h, layers 3 and 4)
+    DIR_MANO_BACKWARD_SCHEDULE(dir::wave_sum, G, L, T, side, center, root_palm, s_sum, s_v, s_gv, s_gvp, tid);
     rodrigues_bwd(G, L, s_full, tid);
     if (tid == 64 && a.g_pose) robust6d_bwd(s_pose, G.groot, a.g_pose + (size_t)b * a.g_pose_stride);
     for (int k = wave; k < 10; k += BT / 64) {

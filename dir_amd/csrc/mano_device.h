@@ -6,10 +6,12 @@
 // because they run the same functions.
 //
 //   1. constants and per-thread primitives     every kernel
-//   2. forward phases of a 256-thread workgroup holding one whole hand in LDS (struct Lds)        backward, fit, fit start, smoother
-//   3. backward phases of the same layout (struct BwdLds)                                         backward, fit
+//   2. forward phases of a 256-thread workgroup holding one whole hand in LDS (struct Lds)        backward, fit, sequence fit, pair fit, fit start, smoother
+//   3. backward phases of the same layout (struct BwdLds)                                         backward, fit, sequence fit, pair fit
+//   4. the schedules: forward_schedule (the six kernels of 2) and DIR_MANO_BACKWARD_SCHEDULE (the four of 3)
 //
-// Everything is __forceinline__.  A phase holds NO barrier: the kernels keep every __syncthreads(), so the synchronisation is read there.
+// Everything is __forceinline__.  A phase holds no barrier; the two schedules hold the barriers of a whole pass and no arithmetic, so the
+// synchronisation of the layer is read in layer 4 and every other __syncthreads() in the kernels.
 // `#pragma clang fp contract(off)` is block-scoped, so a function carries the state of the block it replaced: the forward's robust 6D,
 // Rodrigues and normalisation run uncontracted (they follow the reference's op sequence), the two chain rules at the end run contracted,
 // their recomputation of the forward included -- that recomputation is therefore NOT robust6d() / rodrigues_quat() and is kept as it is.
@@ -554,6 +556,57 @@ __device__ __forceinline__ void robust6d_bwd(const float* p, const float* groot,
     normalize3_bwd(yh0, yh1, yh2, myh, gyh0, gyh1, gyh2);
     g6[0] = gxh0; g6[1] = gxh1; g6[2] = gxh2; g6[3] = gyh0; g6[4] = gyh1; g6[5] = gyh2;
 }
+
+// ===================================================================================================== 4. the schedules of a whole pass
+// The phase calls in their order and the barriers between them, nothing else.  side, center_idx, root_palm: the values the kernel read at its
+// top (layer 2's rule).  t is the thread index inside the hand's 256.
+
+// joint_rotations .. centre.  Before it the kernel has written full (the 45 axis-angles), beta, L.root and v = the shape blend's output, with a
+// barrier behind them where another thread wrote what joint_rotations or joint_regression reads; v becomes v_posed and vert the skinned vertices
+// (vert == v skins in place: the smoother).  No barrier after centre: the kernel sets it, behind whatever else it writes for the next stage.
+__device__ __forceinline__ void forward_schedule(const Lds& L, const dir_mano_tables& t, int side, int center_idx, int root_palm, const float* full,
+                                                 const float* beta, float* v, float* vert, int tid) {
+    joint_rotations(L, full, tid);
+    joint_regression(L, t, beta, tid);
+    __syncthreads();
+    pose_blend(L, t, v, tid);
+    chain(L, tid);
+    __syncthreads();
+    a_primes(L, tid);
+    __syncthreads();
+    skinning(L, t, v, vert, tid);
+    __syncthreads();
+    joints(L, side, root_palm, vert, tid);
+    __syncthreads();
+    centre(L, center_idx, tid);
+}
+
+// centre_bwd .. pose_blend_bwd and the barrier behind it.  In: layer 3's gj, gv, sum3 and a zeroed gAt, behind a barrier; vp = v_posed.  Out: gvp,
+// G.gJ, G.gR, G.groot and the pose blend's share in L.pm, all visible to every thread.  WAVE_SUM: pose_blend_bwd's reducer, dir::wave_sum
+// (mano_bwd.hip) or dir::wave_sum_dpp (the fits).
+// A macro, not a function like forward_schedule: with these calls one inlining level further down the compiler forwards chain_bwd's stores to
+// B.gJ differently and orders the operands of its sums differently, and dir_mano_backward_pair and every fit then give other bits than with the
+// calls written out in the kernel (found on the MI355X; mano_backward_kernel's code differs in 2,800 lines of 5,600).  As a macro the
+// kernels' code is what the written-out calls gave, instruction for instruction.  forward_schedule has no such effect.
+#define DIR_MANO_BACKWARD_SCHEDULE(WAVE_SUM, G, L, t, side, center_idx, root_palm, sum3, vp, gv, gvp, tid) \
+    do {                                                                                                   \
+        dir::mano::centre_bwd(G, center_idx, sum3, tid);                                                   \
+        __syncthreads();                                                                                   \
+        dir::mano::joints_bwd(G, side, root_palm, gv, tid);                                                \
+        __syncthreads();                                                                                   \
+        dir::mano::skinning_bwd(L, t, gv, gvp, tid);                                                       \
+        dir::mano::a_primes_grad(G, t, gv, vp, tid);                                                       \
+        __syncthreads();                                                                                   \
+        dir::mano::a_primes_bwd(G, L, tid);                                                                \
+        __syncthreads();                                                                                   \
+        dir::mano::chain_bwd(G, L, tid);                                                                   \
+        __syncthreads();                                                                                   \
+        dir::mano::chain_root_bwd(G, tid);                                                                 \
+        __syncthreads();                                                                                   \
+        dir::mano::root_split_bwd(G, tid);                                                                 \
+        dir::mano::pose_blend_bwd<WAVE_SUM>(L, t, gvp, tid);                                               \
+        __syncthreads();                                                                                   \
+    } while (0)
 
 }  // namespace mano
 

@@ -2,8 +2,8 @@
 // further variable, and a capsule-per-bone collision term between them.  The rule, the order of every operation and the status bits are written
 // out in include/dir_hip.h ("MANO fitting: two hands together"); tests/helpers/mano_pair_fit_ref.py restates it in torch.
 //
-// One 512-thread workgroup per pair: threads 0-255 run the left slot and 256-511 the right through the SAME phases mano_fit_kernel runs
-// (mano_device.h / mano_fit_device.h, with the thread index taken modulo 256), each on its own set of LDS arrays; the barriers are workgroup wide,
+// One 512-thread workgroup per pair: threads 0-255 run the left slot and 256-511 the right through the SAME schedules and fit pieces mano_fit_kernel
+// runs (mano_device.h / mano_fit_device.h, with the thread index taken modulo 256), each on its own set of LDS arrays; the barriers are workgroup wide,
 // so after centre() both hands' joints of the same iterate are in LDS.  40 threads (one bone of one hand each) then walk the other hand's 20 bones
 // in order, 42 threads gather the bones' sums into the joint cotangents, and both backwards run.  No recomputed forward, no traffic between
 // workgroups, no atomics.  Where no capsule pair is active nothing is added, and both hands get dir_mano_fit's bits.
@@ -17,18 +17,15 @@ using dir::finite;
 using dir::bone::kChild;
 using dir::bone::kParent;
 
-constexpr int ST = DIR_MANO_FIT_STATE, OST = DIR_MANO_FIT_PAIR_STATE;
+constexpr int OST = DIR_MANO_FIT_PAIR_STATE;
 constexpr int PT = 2 * BT;               // the pair's workgroup
 
 struct PairArgs {
     dir_mano_tables t[2];
     dir_mano_fit_hand h[2];
     dir_mano_fit_pair_args p;
-    float kv, kj, kuv;                   // as mano_fit.hip's
-    float k_pca, k_beta, k_init;
-    float lr[4], b1, b2, eps;
+    fit::Rule r;                         // as mano_fit.hip's
     float k_col, k_off, k_oi, lr_o;      // 2 w_col / 400 (formed in double, rounded once), 2 w_off, 2 w_off_init
-    int iters;
 };
 
 __global__ __launch_bounds__(PT) void mano_fit_pair_kernel(PairArgs args) {
@@ -72,45 +69,18 @@ __global__ __launch_bounds__(PT) void mano_fit_pair_kernel(PairArgs args) {
     const float* s_cam = s_p + 61;
 
     // ================================================================ start: each hand's row as mano_fit_kernel reads it, then o and the radii
-    float pb1 = 1.f, pb2 = 1.f;          // this hand's b1^t, b2^t
-    int t_step = 0;
-    if (a.state) {
-        t_step = __float_as_int(a.state[b * ST + 130]);
-        if (t_step > 0) { pb1 = a.state[b * ST + 128]; pb2 = a.state[b * ST + 129]; }
-    }
+    float pb1, pb2;                      // this hand's b1^t, b2^t
+    int t_step;
+    fit::load_clock(a.state, b, pb1, pb2, t_step);
     float po1 = 1.f, po2 = 1.f;          // o's
     int t_o = 0;
     if (pa.o_state) {
         t_o = __float_as_int(pa.o_state[b * OST + 8]);
         if (t_o > 0) { po1 = pa.o_state[b * OST + 6]; po2 = pa.o_state[b * OST + 7]; }
     }
-    int bad_p = 0, bad_t = 0, bad_o = 0;
-    if (lt < 64) {
-        const float x = a.p0[b * 64 + lt];
-        const float an = a.anchor ? a.anchor[b * 64 + lt] : x;
-        s_p0[lt] = x; s_p[lt] = x; s_anchor[lt] = an;
-        s_m[lt] = a.state ? a.state[b * ST + lt] : 0.f;
-        s_vv[lt] = a.state ? a.state[b * ST + 64 + lt] : 0.f;
-        bad_p = !finite(x) || !finite(an);
-    }
-    if (a.verts_t)
-        for (int i = lt; i < NV3; i += BT) bad_t |= !finite(a.verts_t[b * NV3 + i]);
-    if (lt < 21) {
-        if (a.joints_t) {
-            const float c = a.joints_conf ? a.joints_conf[b * 21 + lt] : 1.f;
-            if (c > 0.f) {
-                const float* t = a.joints_t + (b * 21 + lt) * 3;
-                bad_t |= !finite(c) || !finite(t[0]) || !finite(t[1]) || !finite(t[2]);
-            }
-        }
-        if (a.uv_t) {
-            const float d = a.uv_conf ? a.uv_conf[b * 21 + lt] : 1.f;
-            if (d > 0.f) {
-                const float* t = a.uv_t + (b * 21 + lt) * 2;
-                bad_t |= !finite(d) || !finite(t[0]) || !finite(t[1]);
-            }
-        }
-    }
+    const int bad_p = fit::load_row(a, b, s_p0, s_p, s_anchor, s_m, s_vv, lt);
+    const int bad_t = fit::targets_nonfinite(a, b, lt);
+    int bad_o = 0;
     const float c_o = pa.o_target ? (pa.o_conf ? pa.o_conf[b] : 1.f) : 0.f;
     const bool use_ot = c_o > 0.f;                    // selected, never multiplied by 0
     if (lt >= 64 && lt < 84) {
@@ -143,32 +113,20 @@ __global__ __launch_bounds__(PT) void mano_fit_pair_kernel(PairArgs args) {
     for (int it = 0;; ++it) {
         asm volatile("" : "+v"(lt));
         lane = lt & 63; wave = lt >> 6;
-        // ================================================================ forward at s_p (mano_device.h, layer 2)
+        // ================================================================ forward at s_p (mano_device.h, layers 2 and 4)
         if (lt < 45) s_full[lt] = pca_axis_angle(T, s_pose + 6, lt);
         shape_blend(T, s_beta, s_v, lt);
         if (lt == 64) { int reflect; robust6d(s_pose, L.root, reflect); s_flag2[hand] = reflect; }
         __syncthreads();
-        joint_rotations(L, s_full, lt);
-        joint_regression(L, T, s_beta, lt);
-        __syncthreads();
-        pose_blend(L, T, s_v, lt);
-        chain(L, lt);
-        __syncthreads();
-        a_primes(L, lt);
-        __syncthreads();
-        skinning(L, T, s_v, s_vert, lt);
-        __syncthreads();
-        joints(L, side, root_palm, s_vert, lt);
-        __syncthreads();
-        centre(L, center, lt);
+        forward_schedule(L, T, side, center, root_palm, s_full, s_beta, s_v, s_vert, lt);
         __syncthreads();
 
         // ================================================================ residuals of each hand; the joints in the common frame
-        const bool last = it >= args.iters || !(alive || other_alive || o_alive);       // uniform
+        const bool last = it >= args.r.iters || !(alive || other_alive || o_alive);       // uniform
         const bool want_mse = it == 0 || last;
         const bool run_col = coupled && (want_mse || (grad_col && !last));
         float red[11] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        fit::residuals(a, b, L, G, s_vert, s_gv, s_cam, use_v, use_j, use_uv, args.kv, args.kj, args.kuv, lt, red);
+        fit::residuals(a, b, L, G, s_vert, s_gv, s_cam, use_v, use_j, use_uv, args.r.kv, args.r.kj, args.r.kuv, lt, red);
         fit::residual_partials(red, want_mse, s_red, lane, wave);
         if (lt < 48) { G.gAt[lt] = 0.f; }
         if (run_col && lt >= 64 && lt < 64 + 63) {
@@ -261,30 +219,11 @@ __global__ __launch_bounds__(PT) void mano_fit_pair_kernel(PairArgs args) {
         if (last) break;
         __syncthreads();                                                  // the gather wrote gj and s_sum, which centre_bwd reads
 
-        // ================================================================ backward (mano_device.h, layer 3), the gradient into s_g
-        centre_bwd(G, center, s_sum, lt);
-        __syncthreads();
-        joints_bwd(G, side, root_palm, s_gv, lt);
-        __syncthreads();
-        skinning_bwd(L, T, s_gv, s_gvp, lt);
-        a_primes_grad(G, T, s_gv, s_v, lt);
-        __syncthreads();
-        a_primes_bwd(G, L, lt);
-        __syncthreads();
-        chain_bwd(G, L, lt);
-        __syncthreads();
-        chain_root_bwd(G, lt);
-        __syncthreads();
-        root_split_bwd(G, lt);
-        pose_blend_bwd<dir::wave_sum_dpp>(L, T, s_gvp, lt);
-        __syncthreads();
+        // ================================================================ backward (mano_device.h, layers 3 and 4), the gradient into s_g
+        DIR_MANO_BACKWARD_SCHEDULE(dir::wave_sum_dpp, G, L, T, side, center, root_palm, s_sum, s_v, s_gv, s_gvp, lt);
         rodrigues_bwd(G, L, s_full, lt);
         if (lt == 64) robust6d_bwd(s_pose, G.groot, s_g);
-        for (int k = wave; k < 10; k += BT / 64) {
-            const float acc = shape_blend_bwd<dir::wave_sum_dpp>(G, T, s_gvp, k, lane);
-            if (lane == 0) s_g[51 + k] = acc;
-        }
-        if (lt >= 128 && lt < 131) s_g[61 + lt - 128] = s_sum[3 + lt - 128];
+        fit::gradient_tail(G, T, s_gvp, s_sum, s_g, lt);
         __syncthreads();
         if (lt < 45) s_g[6 + lt] = pca_bwd(G, T, lt);
         __syncthreads();
@@ -292,12 +231,12 @@ __global__ __launch_bounds__(PT) void mano_fit_pair_kernel(PairArgs args) {
         // ================================================================ the priors' gradients and one Adam step per hand; the fifth group, o
         float p_new = 0.f, m_new = 0.f, v_new = 0.f;
         int bad = 0, bad_step_o = 0;
-        const float pb1n = pb1 * args.b1, pb2n = pb2 * args.b2, po1n = po1 * args.b1, po2n = po2 * args.b2;
+        const float pb1n = pb1 * args.r.b1, pb2n = pb2 * args.r.b2, po1n = po1 * args.r.b1, po2n = po2 * args.r.b2;
         if (lt < 64 && alive) {
             const float p = s_p[lt];
-            const float g = fit::prior_gradient(lt, s_g[lt], p, s_anchor[lt], args.k_pca, args.k_beta, args.k_init);
+            const float g = fit::prior_gradient(lt, s_g[lt], p, s_anchor[lt], args.r.k_pca, args.r.k_beta, args.r.k_init);
             p_new = p; m_new = s_m[lt]; v_new = s_vv[lt];
-            bad = !fit::adam(g, args.lr[fit::group_of(lt)], args.b1, args.b2, args.eps, pb1n, pb2n, p_new, m_new, v_new);
+            bad = !fit::adam(g, args.r.lr[fit::group_of(lt)], args.r.b1, args.r.b2, args.r.eps, pb1n, pb2n, p_new, m_new, v_new);
         }
         if (tid >= 64 && tid < 67 && o_alive) {
 #pragma clang fp contract(off)
@@ -307,7 +246,7 @@ __global__ __launch_bounds__(PT) void mano_fit_pair_kernel(PairArgs args) {
             if (use_ot) g = g + (args.k_off * c_o) * (o - s_ot[c]);
             g = g + args.k_oi * (o - s_oa[c]);
             p_new = o; m_new = s_om[c]; v_new = s_ov[c];
-            bad_step_o = !fit::adam(g, args.lr_o, args.b1, args.b2, args.eps, po1n, po2n, p_new, m_new, v_new);
+            bad_step_o = !fit::adam(g, args.lr_o, args.r.b1, args.r.b2, args.r.eps, po1n, po2n, p_new, m_new, v_new);
         }
         const bool bad_l = __syncthreads_or(bad && hand == 0) != 0, bad_r = __syncthreads_or(bad && hand == 1) != 0;
         const bool bad_o_step = __syncthreads_or(bad_step_o) != 0;
@@ -331,22 +270,10 @@ __global__ __launch_bounds__(PT) void mano_fit_pair_kernel(PairArgs args) {
 
     // ================================================================ outputs at the final iterate (the forward above ran at it)
     __syncthreads();
-    if (a.verts)
-        for (int i = lt; i < NV3; i += BT) a.verts[b * NV3 + i] = p0_bad ? 0.f : s_vert[i] - L.c[i % 3];
-    if (a.joints && lt < 63) a.joints[b * 63 + lt] = p0_bad ? 0.f : L.jtr[lt] - L.c[lt % 3];
-    if (a.joint_uv && lt >= 64 && lt < 64 + 42) {
-        const int i = lt - 64, j = i >> 1, c = i & 1;
-        a.joint_uv[b * 42 + i] = p0_bad ? 0.f : s_cam[0] * (L.jtr[3 * j + c] - L.c[c]) + (c ? s_cam[2] : s_cam[1]);
-    }
-    if (lt < 64) {
-        a.p_out[b * 64 + lt] = pass ? s_p0[lt] : s_p[lt];
-        if (a.state && !pass) { a.state[b * ST + lt] = s_m[lt]; a.state[b * ST + 64 + lt] = s_vv[lt]; }
-    }
+    fit::write_outputs(a, b, L, s_vert, s_cam, p0_bad, lt);
+    fit::store_row(a, b, pass, s_p0, s_p, s_m, s_vv, lt);
     if (lt == 64) {
-        if (a.state && !pass) {
-            a.state[b * ST + 128] = pb1; a.state[b * ST + 129] = pb2;
-            a.state[b * ST + 130] = __int_as_float(t_step); a.state[b * ST + 131] = 0.f;
-        }
+        if (a.state && !pass) fit::store_clock(a.state, b, pb1, pb2, t_step);
         if (a.status) a.status[b] = status | (p0_bad ? 0 : s_flag2[hand]);
     }
     if (a.mse && lt >= 128 && lt < 134) a.mse[b * 6 + lt - 128] = p0_bad ? 0.f : s_mse[lt - 128];
@@ -373,30 +300,20 @@ extern "C" int dir_mano_fit_pair(const dir_mano_tables* tables_host, const dir_m
     using namespace dir;
     if (B == 0) return DIR_OK;
     DIR_REQUIRE(B > 0 && tables_host && hands_host && opts_host && pair_host && pair_opts_host, "dir_mano_fit_pair: bad arguments");
-    const dir_mano_fit_opts& o = *opts_host;
     const dir_mano_fit_pair_opts& q = *pair_opts_host;
-    DIR_REQUIRE(o.iters >= 0, "dir_mano_fit_pair: iters must be >= 0");
-    for (float w : {o.w_verts, o.w_joints, o.w_uv, o.w_pca, o.w_beta, o.w_init, o.lr[0], o.lr[1], o.lr[2], o.lr[3], q.w_col, q.w_off, q.w_off_init, q.lr_o})
-        DIR_REQUIRE(w >= 0.f && w <= 3.4e38f, "dir_mano_fit_pair: weights and learning rates must be finite and >= 0");
-    DIR_REQUIRE(o.b1 >= 0.f && o.b1 < 1.f && o.b2 >= 0.f && o.b2 < 1.f && o.eps > 0.f, "dir_mano_fit_pair: need 0 <= b1, b2 < 1 and eps > 0");
+    PairArgs a;
+    if (int rc = mano::fit::check_opts(*opts_host, {q.w_col, q.w_off, q.w_off_init, q.lr_o}, "dir_mano_fit_pair", a.r)) return rc;
     const dir_mano_fit_pair_args& p = *pair_host;
     DIR_REQUIRE(p.o0 && p.offset_out && p.radii[0] && p.radii[1], "dir_mano_fit_pair: null pointer (o0 / offset_out / radii)");
     DIR_REQUIRE(!p.o_conf || p.o_target, "dir_mano_fit_pair: o_conf without o_target");
-    PairArgs a;
     for (int h = 0; h < 2; ++h) {
         const dir_mano_tables& t = tables_host[h];
         if (int rc = mano::check_mano_tables(t, "dir_mano_fit_pair")) return rc;
-        const dir_mano_fit_hand& f = hands_host[h];
-        DIR_REQUIRE(f.p0 && f.p_out, "dir_mano_fit_pair: null pointer (p0 / p_out)");
-        DIR_REQUIRE((!f.joints_conf || f.joints_t) && (!f.uv_conf || f.uv_t), "dir_mano_fit_pair: confidences without their target");
+        if (int rc = mano::fit::check_hand(hands_host[h], "dir_mano_fit_pair")) return rc;
         a.t[h] = t;
-        a.h[h] = f;
+        a.h[h] = hands_host[h];
     }
     a.p = p;
-    a.kv = (float)(2.0 * o.w_verts / 778.0); a.kj = (float)(2.0 * o.w_joints / 21.0); a.kuv = (float)(2.0 * o.w_uv / 21.0);
-    a.k_pca = 2.f * o.w_pca; a.k_beta = 2.f * o.w_beta; a.k_init = 2.f * o.w_init;
-    for (int g = 0; g < 4; ++g) a.lr[g] = o.lr[g];
-    a.b1 = o.b1; a.b2 = o.b2; a.eps = o.eps; a.iters = o.iters;
     a.k_col = (float)(2.0 * q.w_col / 400.0); a.k_off = 2.f * q.w_off; a.k_oi = 2.f * q.w_off_init; a.lr_o = q.lr_o;
     DIR_LAUNCH(mano_fit_pair_kernel, dim3(B), dim3(PT), 0, (hipStream_t)stream, a);
     return check_launch("dir_mano_fit_pair");

@@ -8,8 +8,10 @@
 //   mano_fit_seq_init_kernel     (N, hands)  classifies each frame (inert / no data), copies p0 into copy 0, finds the frame's sequence
 //   mano_fit_seq_shape_kernel    (S, hands)  FIRST = true: the shared shape's start and prior centre; false: step 6, the fixed tree over the
 //                                            frames' beta gradients and one Adam step on the shape
-//   mano_fit_seq_kernel          (N, hands)  FINAL = false: one iteration of one frame, mano_fit_kernel's shape (256 threads, the hand in LDS, the
-//                                            phases of mano_device.h, residuals and Adam of mano_fit_device.h); true: the forward-only pass for the outputs
+//   mano_fit_seq_kernel          (N, hands)  FINAL = false: one iteration of one frame, mano_fit_kernel's shape (256 threads, the hand in LDS, the two
+//                                            schedules of mano_device.h; residuals, gradient tail and Adam of mano_fit_device.h); true: the forward-only
+//                                            pass and mano_fit_device.h's output block
+// The init kernel runs the target scan mano_fit_kernel runs, and the entry point the same checks of the options and the hands (mano_fit_device.h).
 //
 // fp32 throughout, every reduction in a fixed order, no atomics, nothing allocated: a sequence gives the same bits alone, in any slot of any ragged
 // batch and in either hand slot.
@@ -48,9 +50,9 @@ struct SeqArgs {
     SeqWork w;
     const int32_t* seq_start;
     int32_t* seq_status;
-    float kv, kj, kuv, k_pca, k_beta, k_init, lr[4], b1, b2, eps;
+    fit::Rule r;
     float kt_root, kt_pca, kt_cam;       // 2 w_t_*
-    int share, N, S, hands, iters;
+    int share, N, S, hands;
     int cur, first;                      // which copy holds the iterate that is read; the first iteration of the call (it writes mse before)
 };
 
@@ -64,7 +66,7 @@ __global__ __launch_bounds__(BT) void mano_fit_seq_init_kernel(SeqArgs args) {
     const int h = blockIdx.y, tid = threadIdx.x;
     const dir_mano_fit_hand& a = args.h[h];
     const size_t b = blockIdx.x, row = (size_t)h * args.N + b;
-    int bad_p = 0, bad_t = 0;
+    int bad_p = 0;
     if (tid < 64) {
         const float x = a.p0[b * 64 + tid];
         const float an = a.anchor ? a.anchor[b * 64 + tid] : x;
@@ -73,24 +75,7 @@ __global__ __launch_bounds__(BT) void mano_fit_seq_init_kernel(SeqArgs args) {
     }
     if (args.own_state[h])
         for (int i = tid; i < ST; i += BT) args.state[h][b * ST + i] = 0.f;
-    if (a.verts_t)
-        for (int i = tid; i < NV3; i += BT) bad_t |= !finite(a.verts_t[b * NV3 + i]);
-    if (tid < 21) {
-        if (a.joints_t) {
-            const float c = a.joints_conf ? a.joints_conf[b * 21 + tid] : 1.f;
-            if (c > 0.f) {
-                const float* t = a.joints_t + (b * 21 + tid) * 3;
-                bad_t |= !finite(c) || !finite(t[0]) || !finite(t[1]) || !finite(t[2]);
-            }
-        }
-        if (a.uv_t) {
-            const float d = a.uv_conf ? a.uv_conf[b * 21 + tid] : 1.f;
-            if (d > 0.f) {
-                const float* t = a.uv_t + (b * 21 + tid) * 2;
-                bad_t |= !finite(d) || !finite(t[0]) || !finite(t[1]);
-            }
-        }
-    }
+    const int bad_t = fit::targets_nonfinite(a, b, tid);
     const bool inert = __syncthreads_or(bad_p) != 0;
     const bool nodata = __syncthreads_or(bad_t) != 0;
     if (tid == 0) {
@@ -149,12 +134,12 @@ template <bool FIRST> __global__ __launch_bounds__(RL) void mano_fit_seq_shape_k
         if (tid < 10) {
             t_step = __float_as_int(st[22]);
             const float pb1 = t_step > 0 ? st[20] : 1.f, pb2 = t_step > 0 ? st[21] : 1.f;
-            pb1n = pb1 * args.b1; pb2n = pb2 * args.b2;
+            pb1n = pb1 * args.r.b1; pb2n = pb2 * args.r.b2;
             float g = s_part[0][tid] + s_part[1][tid] + s_part[2][tid] + s_part[3][tid];
             b_new = args.w.sb[srow * 10 + tid];
-            g = fit::prior_gradient(51 + tid, g, b_new, args.w.sanchor[srow * 10 + tid], args.k_pca, args.k_beta, args.k_init);
+            g = fit::prior_gradient(51 + tid, g, b_new, args.w.sanchor[srow * 10 + tid], args.r.k_pca, args.r.k_beta, args.r.k_init);
             m_new = st[tid]; v_new = st[10 + tid];
-            bad = !fit::adam(g, args.lr[2], args.b1, args.b2, args.eps, pb1n, pb2n, b_new, m_new, v_new);
+            bad = !fit::adam(g, args.r.lr[2], args.r.b1, args.r.b2, args.r.eps, pb1n, pb2n, b_new, m_new, v_new);
         }
         if (__syncthreads_or(bad)) {
             if (tid == 0) args.w.sflags[srow] = sf | F_FROZEN;
@@ -221,8 +206,7 @@ template <bool FINAL> __global__ __launch_bounds__(BT) void mano_fit_seq_kernel(
     int t_step = 0;
     bool has[2] = {false, false};
     if constexpr (!FINAL) {
-        t_step = __float_as_int(st[130]);
-        if (t_step > 0) { pb1 = st[128]; pb2 = st[129]; }
+        fit::load_clock(st, 0, pb1, pb2, t_step);
         if (args.kt_root > 0.f || args.kt_pca > 0.f || args.kt_cam > 0.f) {
             int s0, s1;
             seq_range(args, seq, s0, s1);
@@ -245,7 +229,7 @@ template <bool FINAL> __global__ __launch_bounds__(BT) void mano_fit_seq_kernel(
     const bool data = !(fl & (F_INERT | F_NODATA));
     const bool use_v = a.verts_t && data, use_j = a.joints_t && data, use_uv = a.uv_t && data;
 
-    // ================================================================ forward at s_p (mano_device.h, layer 2)
+    // ================================================================ forward at s_p (mano_device.h, layers 2 and 4)
     if (tid < 45) s_full[tid] = pca_axis_angle(T, s_pose + 6, tid);
     shape_blend(T, s_beta, s_v, tid);
     if (tid == 64) { int reflect; robust6d(s_pose, L.root, reflect); s_flag = reflect; }
@@ -253,25 +237,13 @@ template <bool FINAL> __global__ __launch_bounds__(BT) void mano_fit_seq_kernel(
         if ((tid == 65 || tid == 66) && has[tid - 65] && args.kt_root > 0.f) { int reflect; robust6d(s_nb[tid - 65], s_nbR[tid - 65], reflect); }
     }
     __syncthreads();
-    joint_rotations(L, s_full, tid);
-    joint_regression(L, T, s_beta, tid);
-    __syncthreads();
-    pose_blend(L, T, s_v, tid);
-    chain(L, tid);
-    __syncthreads();
-    a_primes(L, tid);
-    __syncthreads();
-    skinning(L, T, s_v, s_vert, tid);
-    __syncthreads();
-    joints(L, side, root_palm, s_vert, tid);
-    __syncthreads();
-    centre(L, center, tid);
+    forward_schedule(L, T, side, center, root_palm, s_full, s_beta, s_v, s_vert, tid);
     __syncthreads();
 
     // ================================================================ residuals: the cotangents gV, gJ, gU; the mean squared residuals at p0 and at the end
     const bool want_mse = FINAL || args.first;
     float red[11] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    fit::residuals(a, b, L, G, s_vert, s_gv, s_cam, use_v, use_j, use_uv, args.kv, args.kj, args.kuv, tid, red);
+    fit::residuals(a, b, L, G, s_vert, s_gv, s_cam, use_v, use_j, use_uv, args.r.kv, args.r.kj, args.r.kuv, tid, red);
     fit::residual_partials(red, want_mse, s_red, lane, wave);
     if (tid < 48) { G.gAt[tid] = 0.f; }
     __syncthreads();
@@ -279,42 +251,21 @@ template <bool FINAL> __global__ __launch_bounds__(BT) void mano_fit_seq_kernel(
     __syncthreads();
     if (want_mse && tid < 3 && a.mse) {
         const float mse = p0_bad ? 0.f : fit::mean_sq(s_sum, use_v, tid);
-        if (!FINAL || inert || args.iters == 0) a.mse[b * 6 + tid] = mse;      // at p0: the first iteration wrote it for the frames that step
+        if (!FINAL || inert || args.r.iters == 0) a.mse[b * 6 + tid] = mse;      // at p0: the first iteration wrote it for the frames that step
         if (FINAL) a.mse[b * 6 + 3 + tid] = mse;
     }
 
     if constexpr (FINAL) {
         // ================================================================ outputs at the final iterate
-        if (a.verts)
-            for (int i = tid; i < NV3; i += BT) a.verts[b * NV3 + i] = p0_bad ? 0.f : s_vert[i] - L.c[i % 3];
-        if (a.joints && tid < 63) a.joints[b * 63 + tid] = p0_bad ? 0.f : L.jtr[tid] - L.c[tid % 3];
-        if (a.joint_uv && tid >= 64 && tid < 64 + 42) {
-            const int i = tid - 64, j = i >> 1, c = i & 1;
-            a.joint_uv[b * 42 + i] = p0_bad ? 0.f : s_cam[0] * (L.jtr[3 * j + c] - L.c[c]) + (c ? s_cam[2] : s_cam[1]);
-        }
+        fit::write_outputs(a, b, L, s_vert, s_cam, p0_bad, tid);
         if (tid < 64) a.p_out[b * 64 + tid] = s_p[tid];
         if (tid == 64 && a.status) a.status[b] = fl | (p0_bad ? 0 : s_flag);
         if (tid == 66 && !inert && __float_as_int(st[130]) == 0) { st[128] = 1.f; st[129] = 1.f; st[131] = 0.f; }      // no step taken: the state dir_mano_fit returns, P1 = P2 = 1
         if (tid == 65 && hand == 0 && n < args.S && args.seq_status)
             for (int hh = 0; hh < args.hands; ++hh) args.seq_status[(size_t)hh * args.S + n] = args.w.sflags[(size_t)hh * args.S + n];
     } else {
-        // ================================================================ backward (mano_device.h, layer 3), the gradient into s_g
-        centre_bwd(G, center, s_sum, tid);
-        __syncthreads();
-        joints_bwd(G, side, root_palm, s_gv, tid);
-        __syncthreads();
-        skinning_bwd(L, T, s_gv, s_gvp, tid);
-        a_primes_grad(G, T, s_gv, s_v, tid);
-        __syncthreads();
-        a_primes_bwd(G, L, tid);
-        __syncthreads();
-        chain_bwd(G, L, tid);
-        __syncthreads();
-        chain_root_bwd(G, tid);
-        __syncthreads();
-        root_split_bwd(G, tid);
-        pose_blend_bwd<dir::wave_sum_dpp>(L, T, s_gvp, tid);
-        __syncthreads();
+        // ================================================================ backward (mano_device.h, layers 3 and 4), the gradient into s_g
+        DIR_MANO_BACKWARD_SCHEDULE(dir::wave_sum_dpp, G, L, T, side, center, root_palm, s_sum, s_v, s_gv, s_gvp, tid);
         rodrigues_bwd(G, L, s_full, tid);
         if (tid == 64) {
             if (args.kt_root > 0.f) {                                    // the temporal root term, on the 3x3 cotangent: t - 1 first, then t + 1
@@ -325,11 +276,7 @@ template <bool FINAL> __global__ __launch_bounds__(BT) void mano_fit_seq_kernel(
             }
             robust6d_bwd(s_pose, G.groot, s_g);
         }
-        for (int k = wave; k < 10; k += BT / 64) {
-            const float acc = shape_blend_bwd<dir::wave_sum_dpp>(G, T, s_gvp, k, lane);
-            if (lane == 0) s_g[51 + k] = acc;
-        }
-        if (tid >= 128 && tid < 131) s_g[61 + tid - 128] = s_sum[3 + tid - 128];
+        fit::gradient_tail(G, T, s_gvp, s_sum, s_g, tid);
         __syncthreads();
         if (tid < 45) s_g[6 + tid] = pca_bwd(G, T, tid);
         __syncthreads();
@@ -337,7 +284,7 @@ template <bool FINAL> __global__ __launch_bounds__(BT) void mano_fit_seq_kernel(
         // ================================================================ the priors' and the temporal gradients, one Adam step (include/dir_hip.h gives this order)
         float p_new = 0.f, m_new = 0.f, v_new = 0.f;
         int bad = 0;
-        const float pb1n = pb1 * args.b1, pb2n = pb2 * args.b2;
+        const float pb1n = pb1 * args.r.b1, pb2n = pb2 * args.r.b2;
         const bool shared_comp = share && tid >= 51 && tid < 61;          // the shape's step is mano_fit_seq_shape_kernel's
         if (tid < 64) {
             const float p = s_p[tid];
@@ -345,14 +292,14 @@ template <bool FINAL> __global__ __launch_bounds__(BT) void mano_fit_seq_kernel(
             if (shared_comp) {
                 args.w.gb[row * 10 + tid - 51] = s_g[tid];
             } else {
-                float g = fit::prior_gradient(tid, s_g[tid], p, s_anchor[tid], args.k_pca, args.k_beta, args.k_init);
+                float g = fit::prior_gradient(tid, s_g[tid], p, s_anchor[tid], args.r.k_pca, args.r.k_beta, args.r.k_init);
                 const float kt = tid >= 6 && tid < 51 ? args.kt_pca : tid >= 61 ? args.kt_cam : 0.f;
                 if (kt > 0.f) {
 #pragma clang fp contract(off)
                     if (has[0]) g = g + kt * (p - s_nb[0][tid]);
                     if (has[1]) g = g + kt * (p - s_nb[1][tid]);
                 }
-                bad = !fit::adam(g, args.lr[fit::group_of(tid)], args.b1, args.b2, args.eps, pb1n, pb2n, p_new, m_new, v_new);
+                bad = !fit::adam(g, args.r.lr[fit::group_of(tid)], args.r.b1, args.r.b2, args.r.eps, pb1n, pb2n, p_new, m_new, v_new);
             }
         }
         if (__syncthreads_or(bad)) {          // the step is not taken: the frame is frozen at this iterate, its state stays
@@ -363,7 +310,7 @@ template <bool FINAL> __global__ __launch_bounds__(BT) void mano_fit_seq_kernel(
                 nxt[tid] = shared_comp ? cur[tid] : p_new;
                 if (!shared_comp) { st[tid] = m_new; st[64 + tid] = v_new; }
             }
-            if (tid == 64) { st[128] = pb1n; st[129] = pb2n; st[130] = __int_as_float(t_step + 1); st[131] = 0.f; }
+            if (tid == 64) fit::store_clock(st, 0, pb1n, pb2n, t_step + 1);
         }
     }
 }
@@ -382,19 +329,15 @@ extern "C" int dir_mano_fit_sequence(const dir_mano_tables* tables_host, const d
     if (N == 0 && S == 0) return DIR_OK;
     DIR_REQUIRE(N > 0 && S > 0 && S <= N && (hands == 1 || hands == 2) && tables_host && hands_host && opts_host && seq_opts_host && seq_start,
                 "dir_mano_fit_sequence: bad arguments");
-    const dir_mano_fit_opts& o = *opts_host;
     const dir_mano_fit_seq_opts& q = *seq_opts_host;
-    DIR_REQUIRE(o.iters >= 0, "dir_mano_fit_sequence: iters must be >= 0");
-    for (float w : {o.w_verts, o.w_joints, o.w_uv, o.w_pca, o.w_beta, o.w_init, o.lr[0], o.lr[1], o.lr[2], o.lr[3], q.w_t_root, q.w_t_pca, q.w_t_cam})
-        DIR_REQUIRE(w >= 0.f && w <= 3.4e38f, "dir_mano_fit_sequence: weights and learning rates must be finite and >= 0");
-    DIR_REQUIRE(o.b1 >= 0.f && o.b1 < 1.f && o.b2 >= 0.f && o.b2 < 1.f && o.eps > 0.f, "dir_mano_fit_sequence: need 0 <= b1, b2 < 1 and eps > 0");
+    SeqArgs a;
+    if (int rc = mano::fit::check_opts(*opts_host, {q.w_t_root, q.w_t_pca, q.w_t_cam}, "dir_mano_fit_sequence", a.r)) return rc;
     DIR_REQUIRE(work && ((uintptr_t)work & 3) == 0 && work_bytes >= dir_mano_fit_sequence_workspace_bytes(N, S, hands),
                 "dir_mano_fit_sequence: workspace too small (or null, or not 4-byte aligned)");
     if (q.seq_start_host) {
         DIR_REQUIRE(q.seq_start_host[0] == 0 && q.seq_start_host[S] == N, "dir_mano_fit_sequence: seq_start must run from 0 to N");
         for (int s = 0; s < S; ++s) DIR_REQUIRE(q.seq_start_host[s] <= q.seq_start_host[s + 1], "dir_mano_fit_sequence: seq_start must ascend");
     }
-    SeqArgs a;
     const size_t n = N, s = S, hn = (size_t)hands * n, hs = (size_t)hands * s;
     float* w = (float*)work;
     a.w.P = w; w += 2 * hn * 64;
@@ -410,8 +353,7 @@ extern "C" int dir_mano_fit_sequence(const dir_mano_tables* tables_host, const d
         const dir_mano_tables& t = tables_host[h];
         if (int rc = mano::check_mano_tables(t, "dir_mano_fit_sequence")) return rc;
         const dir_mano_fit_hand& f = hands_host[h];
-        DIR_REQUIRE(f.p0 && f.p_out, "dir_mano_fit_sequence: null pointer (p0 / p_out)");
-        DIR_REQUIRE((!f.joints_conf || f.joints_t) && (!f.uv_conf || f.uv_t), "dir_mano_fit_sequence: confidences without their target");
+        if (int rc = mano::fit::check_hand(f, "dir_mano_fit_sequence")) return rc;
         a.t[h] = t;
         a.h[h] = f;
         a.own_state[h] = !f.state; a.state[h] = f.state ? f.state : a.w.state + (size_t)h * n * ST;
@@ -419,21 +361,17 @@ extern "C" int dir_mano_fit_sequence(const dir_mano_tables* tables_host, const d
     }
     if (hands == 1) { a.t[1] = a.t[0]; a.h[1] = a.h[0]; a.state[1] = a.state[0]; a.sstate[1] = a.sstate[0]; a.own_state[1] = a.own_state[0]; a.own_sstate[1] = a.own_sstate[0]; }
     a.seq_start = seq_start; a.seq_status = seq_status;
-    a.kv = (float)(2.0 * o.w_verts / 778.0); a.kj = (float)(2.0 * o.w_joints / 21.0); a.kuv = (float)(2.0 * o.w_uv / 21.0);
-    a.k_pca = 2.f * o.w_pca; a.k_beta = 2.f * o.w_beta; a.k_init = 2.f * o.w_init;
-    for (int g = 0; g < 4; ++g) a.lr[g] = o.lr[g];
-    a.b1 = o.b1; a.b2 = o.b2; a.eps = o.eps; a.iters = o.iters;
     a.kt_root = 2.f * q.w_t_root; a.kt_pca = 2.f * q.w_t_pca; a.kt_cam = 2.f * q.w_t_cam;
     a.share = q.share_betas != 0; a.N = N; a.S = S; a.hands = hands; a.cur = 0; a.first = 0;
     hipStream_t st = (hipStream_t)stream;
     DIR_LAUNCH(mano_fit_seq_init_kernel, dim3(N, hands), dim3(BT), 0, st, a);
     DIR_LAUNCH(mano_fit_seq_shape_kernel<true>, dim3(S, hands), dim3(RL), 0, st, a);
-    for (int it = 0; it < o.iters; ++it) {
+    for (int it = 0; it < a.r.iters; ++it) {
         a.cur = it & 1; a.first = it == 0;
         DIR_LAUNCH(mano_fit_seq_kernel<false>, dim3(N, hands), dim3(BT), 0, st, a);
         if (a.share) DIR_LAUNCH(mano_fit_seq_shape_kernel<false>, dim3(S, hands), dim3(RL), 0, st, a);
     }
-    a.cur = o.iters & 1; a.first = 0;
+    a.cur = a.r.iters & 1; a.first = 0;
     DIR_LAUNCH(mano_fit_seq_kernel<true>, dim3(N, hands), dim3(BT), 0, st, a);
     return check_launch("dir_mano_fit_sequence");
 }

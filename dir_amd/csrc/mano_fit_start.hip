@@ -2,12 +2,13 @@
 // search over the cube's 24 rotations and a least-squares camera put them; the other 55 floats copied.  The rule, the order of every sum and
 // the status bits are written out in include/dir_hip.h ("MANO fitting: closed-form start"); tests/helpers/mano_start_ref.py restates it.
 //
-// One 256-thread workgroup per (sample, hand), as mano_fit_kernel.  The forward at p0 is mano_device.h's phases, run ONCE; what follows is two
+// One 256-thread workgroup per (sample, hand), as mano_fit_kernel.  The forward at p0 is mano_device.h's forward schedule, run ONCE, behind the
+// target scan the fit kernels run (mano_fit_device.h); what follows is two
 // reductions over the 778 vertices (the cross-covariance and the energy before; the energy after), one thread solving Horn's 4 x 4 eigenproblem
 // (horn_rotation.h, the solver dir_procrustes_align runs), 24 threads fitting one camera each over 21 keypoints, and one thread deciding.
 // fp32 throughout, every sum in a fixed order, no atomics, no workspace: a row gives the same bits in any slot of any batch and in either hand slot.
 #include "horn_rotation.h"
-#include "mano_device.h"
+#include "mano_fit_device.h"
 
 namespace {
 
@@ -59,30 +60,13 @@ __global__ __launch_bounds__(BT) void mano_fit_start_kernel(StartArgs args) {
     const float* s_beta = s_p + 51;
 
     // ================================================================ the row and the pass-through test (status bit 1, dir_mano_fit's definition)
-    int bad_p = 0, bad_t = 0;
+    int bad_p = 0;
     if (tid < 64) {
         const float x = a.p0[b * 64 + tid];
         s_p[tid] = x;
         bad_p = !finite(x);
     }
-    if (a.verts_t)
-        for (int i = tid; i < NV3; i += BT) bad_t |= !finite(a.verts_t[b * NV3 + i]);
-    if (tid < 21) {
-        if (a.joints_t) {
-            const float c = a.joints_conf ? a.joints_conf[b * 21 + tid] : 1.f;
-            if (c > 0.f) {
-                const float* t = a.joints_t + (b * 21 + tid) * 3;
-                bad_t |= !finite(c) || !finite(t[0]) || !finite(t[1]) || !finite(t[2]);
-            }
-        }
-        if (a.uv_t) {
-            const float d = a.uv_conf ? a.uv_conf[b * 21 + tid] : 1.f;
-            if (d > 0.f) {
-                const float* t = a.uv_t + (b * 21 + tid) * 2;
-                bad_t |= !finite(d) || !finite(t[0]) || !finite(t[1]);
-            }
-        }
-    }
+    const int bad_t = fit::targets_nonfinite(a, b, tid);
     if (tid < 63) s_jt[tid] = a.joints_t ? a.joints_t[b * 63 + tid] : 0.f;                    // copies: an entry selected out may hold NaN
     if (tid >= 64 && tid < 85) s_jc[tid - 64] = a.joints_conf ? a.joints_conf[b * 21 + tid - 64] : 1.f;
     if (tid >= 128 && tid < 170) s_ut[tid - 128] = a.uv_t ? a.uv_t[b * 42 + tid - 128] : 0.f;
@@ -90,24 +74,12 @@ __global__ __launch_bounds__(BT) void mano_fit_start_kernel(StartArgs args) {
     const bool p0_bad = __syncthreads_or(bad_p) != 0;
     const bool in_bad = __syncthreads_or(bad_t) != 0 || p0_bad;
 
-    // ================================================================ forward at p0 (mano_device.h, layer 2)
+    // ================================================================ forward at p0 (mano_device.h, layers 2 and 4)
     if (tid < 45) s_full[tid] = pca_axis_angle(T, s_pose + 6, tid);
     shape_blend(T, s_beta, s_v, tid);
     if (tid == 64) { int reflect; robust6d(s_pose, L.root, reflect); s_flag = reflect; }
     __syncthreads();
-    joint_rotations(L, s_full, tid);
-    joint_regression(L, T, s_beta, tid);
-    __syncthreads();
-    pose_blend(L, T, s_v, tid);
-    chain(L, tid);
-    __syncthreads();
-    a_primes(L, tid);
-    __syncthreads();
-    skinning(L, T, s_v, s_vert, tid);
-    __syncthreads();
-    joints(L, side, root_palm, s_vert, tid);
-    __syncthreads();
-    centre(L, center, tid);
+    forward_schedule(L, T, side, center, root_palm, s_full, s_beta, s_v, s_vert, tid);
     if (tid >= 64 && tid < 67) s_pi[tid - 64] = center >= 0 ? 0.f : L.J[tid - 64];       // step 1: the pivot
     __syncthreads();
 

@@ -8,7 +8,7 @@
 //                             scalar work (lane 64 the root, lanes 0..14 the fingers, 16..18 the camera, 32..41 the shape); the whole
 //                             workgroup does the blend shapes, the skinning, the history shift and the reductions of the measures.
 //
-// The forward is mano_device.h's phases, the ones mano.hip runs (a first usable frame gives dir_mano_forward's bits), skinning in place; the
+// The forward is mano_device.h's forward schedule over the phases mano.hip runs (a first usable frame gives dir_mano_forward's bits), skinning in place; the
 // One-Euro arithmetic restates smooth.hip's.  No atomics, no workspace, no flags between workgroups, vector stores only: a (sequence, hand)
 // gives the same bits in any slot of any batch and in either hand slot.
 #include <math.h>
@@ -221,21 +221,9 @@ __global__ __launch_bounds__(BT) void mano_para_smooth_kernel(SmoothArgs args) {
         }
     }
 
-    // ================================================================ step 6: the forward from (R_y, a_y, b_y): mano_device.h's phases from the shape blend on
+    // ================================================================ step 6: the forward from (R_y, a_y, b_y): mano_device.h's shape blend and forward schedule
     shape_blend(T, s_beta, s_v, tid);
-    joint_rotations(L, s_full, tid);
-    joint_regression(L, T, s_beta, tid);
-    __syncthreads();
-    pose_blend(L, T, s_v, tid);
-    chain(L, tid);
-    __syncthreads();
-    a_primes(L, tid);
-    __syncthreads();
-    skinning(L, T, s_v, s_v, tid);
-    __syncthreads();
-    joints(L, side, root_palm, s_v, tid);
-    __syncthreads();
-    centre(L, center, tid);
+    forward_schedule(L, T, side, center, root_palm, s_full, s_beta, s_v, s_v, tid);      // skinning in place
     __syncthreads();
     for (int i = tid; i < NV3; i += BT) s_v[i] = s_v[i] - L.c[i % 3];
     if (tid < 63) s_jo[tid] = L.jtr[tid] - L.c[tid % 3];

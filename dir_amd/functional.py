@@ -323,6 +323,52 @@ def regress_backward(w_left, w_right, w_offset, tok, prev_para_left, prev_para_r
 
 MANO_FIT_WEIGHTS = ('w_verts', 'w_joints', 'w_uv', 'w_pca', 'w_beta', 'w_init')
 MANO_FIT_GROUPS = ('root', 'pca', 'betas', 'cam')
+MANO_FIT_PAIR_WEIGHTS = ('w_col', 'w_off', 'w_off_init')
+
+
+def _mano_per_hand(who, hands, dev, ts, shape, what):
+    """One argument of a MANO fitting wrapper -- None, or a list with one tensor or None per hand -- as a checked list of `hands` entries.
+    who: the wrapper's name, which the error carries"""
+    ts = [None] * hands if ts is None else list(ts)
+    assert len(ts) == hands
+    for t in ts:
+        if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape and t.device == dev):
+            raise _capi.DirHipError('%s: %s must be a contiguous float32 %s tensor on %s' % (who, what, list(shape), dev))
+    _capi.require_cuda(*ts)
+    return ts
+
+
+def _mano_fit_opts(who, weights, lr, betas, eps, iters, more=None, more_names=()):
+    """_capi.ManoFitOpts from a wrapper's arguments.  more / more_names: the wrapper's further weights and the names they may carry, part of the same
+    unknown-weight error"""
+    import ctypes as C
+    w = dict(weights or {})
+    unknown = (set(w) - set(MANO_FIT_WEIGHTS)) | (set(more or {}) - set(more_names))
+    if unknown:
+        raise ValueError('%s: unknown weights %s' % (who, sorted(unknown)))
+    return _capi.ManoFitOpts(*[float(w.get(k, 0.0)) for k in MANO_FIT_WEIGHTS], (C.c_float * 4)(*[float(v) for v in lr]), float(betas[0]), float(betas[1]),
+                             float(eps), int(iters))
+
+
+def _mano_fit_hands(who, hands, B, dev, init_lr, verts, joints, joints_conf, joint_uv, uv_conf, anchor, state, para_out, outputs):
+    """The per-hand arguments of mano_fit, mano_fit_pair and mano_fit_sequence (B rows), checked.  -> the list per hand of result dicts para, mse [B,6],
+    status [B] (+ verts, joints, joint_uv with outputs) and the _capi.ManoFitHand array that points into them"""
+    P = _capi.ptr
+    init = _mano_per_hand(who, hands, dev, init_lr, (B, 64), 'init')
+    targets = [_mano_per_hand(who, hands, dev, ts, (B,) + s, what) for ts, s, what in (
+        (verts, (778, 3), 'verts'), (joints, (21, 3), 'joints'), (joints_conf, (21,), 'joints_conf'), (joint_uv, (21, 2), 'joint_uv'), (uv_conf, (21,), 'uv_conf'))]
+    an, st, po = [_mano_per_hand(who, hands, dev, ts, (B, n), what) for ts, n, what in (
+        (anchor, 64, 'anchor'), (state, _capi.MANO_FIT_STATE, 'state'), (para_out, 64, 'para_out'))]
+    res, hs = [], []
+    for h in range(hands):
+        r = {'para': po[h] if po[h] is not None else torch.empty(B, 64, device=dev), 'mse': torch.empty(B, 6, device=dev),
+             'status': torch.empty(B, dtype=torch.int32, device=dev)}
+        if outputs:
+            r.update(verts=torch.empty(B, 778, 3, device=dev), joints=torch.empty(B, 21, 3, device=dev), joint_uv=torch.empty(B, 21, 2, device=dev))
+        hs.append(_capi.ManoFitHand(init[h].data_ptr(), P(an[h]), r['para'].data_ptr(), *[P(t[h]) for t in targets],
+                                    P(r.get('verts')), P(r.get('joints')), P(r.get('joint_uv')), r['mse'].data_ptr(), r['status'].data_ptr(), P(st[h])))
+        res.append(r)
+    return res, (_capi.ManoFitHand * hands)(*hs)
 
 
 def mano_fit(tables_lr, init_lr, verts=None, joints=None, joints_conf=None, joint_uv=None, uv_conf=None, iters=200, lr=(0.1, 0.1, 0.1, 0.1),
@@ -336,41 +382,11 @@ def mano_fit(tables_lr, init_lr, verts=None, joints=None, joints_conf=None, join
     hands = len(init_lr)
     assert hands in (1, 2) and len(tables_lr) == hands
     B, dev = init_lr[0].shape[0], init_lr[0].device
-
-    def per_hand(ts, shape, what):
-        ts = [None] * hands if ts is None else list(ts)
-        assert len(ts) == hands
-        for t in ts:
-            if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape and t.device == dev):
-                raise _capi.DirHipError('mano_fit: %s must be a contiguous float32 %s tensor on %s' % (what, list(shape), dev))
-        _capi.require_cuda(*ts)
-        return ts
-    init = per_hand(init_lr, (B, 64), 'init')
-    tv, tj, cj = per_hand(verts, (B, 778, 3), 'verts'), per_hand(joints, (B, 21, 3), 'joints'), per_hand(joints_conf, (B, 21), 'joints_conf')
-    tu, cu = per_hand(joint_uv, (B, 21, 2), 'joint_uv'), per_hand(uv_conf, (B, 21), 'uv_conf')
-    an, st, po = per_hand(anchor, (B, 64), 'anchor'), per_hand(state, (B, _capi.MANO_FIT_STATE), 'state'), per_hand(para_out, (B, 64), 'para_out')
-    w = dict(weights or {})
-    if set(w) - set(MANO_FIT_WEIGHTS):
-        raise ValueError('mano_fit: unknown weights %s' % sorted(set(w) - set(MANO_FIT_WEIGHTS)))
-    opts = _capi.ManoFitOpts(*[float(w.get(k, 0.0)) for k in MANO_FIT_WEIGHTS], (C.c_float * 4)(*[float(v) for v in lr]), float(betas[0]), float(betas[1]),
-                             float(eps), int(iters))
-    res, hs = [], []
-    for h in range(hands):
-        r = {'para': po[h] if po[h] is not None else torch.empty(B, 64, device=dev), 'mse': torch.empty(B, 6, device=dev),
-             'status': torch.empty(B, dtype=torch.int32, device=dev)}
-        if outputs:
-            r.update(verts=torch.empty(B, 778, 3, device=dev), joints=torch.empty(B, 21, 3, device=dev), joint_uv=torch.empty(B, 21, 2, device=dev))
-        P = _capi.ptr
-        hs.append(_capi.ManoFitHand(init[h].data_ptr(), P(an[h]), r['para'].data_ptr(), P(tv[h]), P(tj[h]), P(cj[h]), P(tu[h]), P(cu[h]),
-                                    P(r.get('verts')), P(r.get('joints')), P(r.get('joint_uv')), r['mse'].data_ptr(), r['status'].data_ptr(), P(st[h])))
-        res.append(r)
+    res, hs = _mano_fit_hands('mano_fit', hands, B, dev, init_lr, verts, joints, joints_conf, joint_uv, uv_conf, anchor, state, para_out, outputs)
+    opts = _mano_fit_opts('mano_fit', weights, lr, betas, eps, iters)
     with torch.cuda.device(dev):
-        _capi.check(_capi.lib().dir_mano_fit((_capi.ManoTables * hands)(*tables_lr), (_capi.ManoFitHand * hands)(*hs), C.byref(opts), hands, B,
-                                             _capi.stream_ptr()), 'dir_mano_fit')
+        _capi.check(_capi.lib().dir_mano_fit((_capi.ManoTables * hands)(*tables_lr), hs, C.byref(opts), hands, B, _capi.stream_ptr()), 'dir_mano_fit')
     return res
-
-
-MANO_FIT_PAIR_WEIGHTS = ('w_col', 'w_off', 'w_off_init')
 
 
 def mano_fit_pair(tables_lr, init_lr, offset0, radii, verts=None, joints=None, joints_conf=None, joint_uv=None, uv_conf=None, iters=200, lr=(0.1, 0.1, 0.1, 0.1),
@@ -383,47 +399,23 @@ def mano_fit_pair(tables_lr, init_lr, offset0, radii, verts=None, joints=None, j
     import ctypes as C
     assert len(init_lr) == 2 and len(tables_lr) == 2 and len(radii) == 2
     B, dev = init_lr[0].shape[0], init_lr[0].device
-
-    def per_hand(ts, shape, what):
-        ts = [None] * 2 if ts is None else list(ts)
-        assert len(ts) == 2
-        for t in ts:
-            if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape and t.device == dev):
-                raise _capi.DirHipError('mano_fit_pair: %s must be a contiguous float32 %s tensor on %s' % (what, list(shape), dev))
-        _capi.require_cuda(*ts)
-        return ts
-    one = lambda t, shape, what: per_hand([t, None], shape, what)[0]  # noqa: E731
-    init = per_hand(init_lr, (B, 64), 'init')
-    tv, tj, cj = per_hand(verts, (B, 778, 3), 'verts'), per_hand(joints, (B, 21, 3), 'joints'), per_hand(joints_conf, (B, 21), 'joints_conf')
-    tu, cu = per_hand(joint_uv, (B, 21, 2), 'joint_uv'), per_hand(uv_conf, (B, 21), 'uv_conf')
-    an, st, po = per_hand(anchor, (B, 64), 'anchor'), per_hand(state, (B, _capi.MANO_FIT_STATE), 'state'), per_hand(para_out, (B, 64), 'para_out')
-    rad = per_hand(radii, (20,), 'radii')
+    res, hs = _mano_fit_hands('mano_fit_pair', 2, B, dev, init_lr, verts, joints, joints_conf, joint_uv, uv_conf, anchor, state, para_out, outputs)
+    one = lambda t, shape, what: _mano_per_hand('mano_fit_pair', 1, dev, [t], shape, what)[0]  # noqa: E731
+    rad = _mano_per_hand('mano_fit_pair', 2, dev, radii, (20,), 'radii')
     o0, ot, oc, oa = one(offset0, (B, 3), 'offset0'), one(offset_target, (B, 3), 'offset_target'), one(offset_conf, (B,), 'offset_conf'), one(offset_anchor, (B, 3), 'offset_anchor')
     ost, oo = one(offset_state, (B, _capi.MANO_FIT_PAIR_STATE), 'offset_state'), one(offset_out, (B, 3), 'offset_out')
     if o0 is None or rad[0] is None or rad[1] is None:
         raise _capi.DirHipError('mano_fit_pair: offset0 and both radii are required')
-    w, pw = dict(weights or {}), dict(pair_weights or {})
-    if set(w) - set(MANO_FIT_WEIGHTS) or set(pw) - set(MANO_FIT_PAIR_WEIGHTS):
-        raise ValueError('mano_fit_pair: unknown weights %s' % sorted((set(w) - set(MANO_FIT_WEIGHTS)) | (set(pw) - set(MANO_FIT_PAIR_WEIGHTS))))
-    opts = _capi.ManoFitOpts(*[float(w.get(k, 0.0)) for k in MANO_FIT_WEIGHTS], (C.c_float * 4)(*[float(v) for v in lr]), float(betas[0]), float(betas[1]),
-                             float(eps), int(iters))
+    pw = dict(pair_weights or {})
+    opts = _mano_fit_opts('mano_fit_pair', weights, lr, betas, eps, iters, pw, MANO_FIT_PAIR_WEIGHTS)
     popts = _capi.ManoFitPairOpts(*[float(pw.get(k, 0.0)) for k in MANO_FIT_PAIR_WEIGHTS], float(lr_offset))
-    res, hs = [], []
     P = _capi.ptr
-    for h in range(2):
-        r = {'para': po[h] if po[h] is not None else torch.empty(B, 64, device=dev), 'mse': torch.empty(B, 6, device=dev),
-             'status': torch.empty(B, dtype=torch.int32, device=dev)}
-        if outputs:
-            r.update(verts=torch.empty(B, 778, 3, device=dev), joints=torch.empty(B, 21, 3, device=dev), joint_uv=torch.empty(B, 21, 2, device=dev))
-        hs.append(_capi.ManoFitHand(init[h].data_ptr(), P(an[h]), r['para'].data_ptr(), P(tv[h]), P(tj[h]), P(cj[h]), P(tu[h]), P(cu[h]),
-                                    P(r.get('verts')), P(r.get('joints')), P(r.get('joint_uv')), r['mse'].data_ptr(), r['status'].data_ptr(), P(st[h])))
-        res.append(r)
     pr = {'offset': oo if oo is not None else torch.empty(B, 3, device=dev), 'col': torch.empty(B, 4, device=dev),
           'pair_status': torch.empty(B, dtype=torch.int32, device=dev)}
     pargs = _capi.ManoFitPairArgs(o0.data_ptr(), P(ot), P(oc), P(oa), (C.c_void_p * 2)(rad[0].data_ptr(), rad[1].data_ptr()), pr['offset'].data_ptr(),
                                   pr['col'].data_ptr(), pr['pair_status'].data_ptr(), P(ost))
     with torch.cuda.device(dev):
-        _capi.check(_capi.lib().dir_mano_fit_pair((_capi.ManoTables * 2)(*tables_lr), (_capi.ManoFitHand * 2)(*hs), C.byref(opts), C.byref(pargs), C.byref(popts),
+        _capi.check(_capi.lib().dir_mano_fit_pair((_capi.ManoTables * 2)(*tables_lr), hs, C.byref(opts), C.byref(pargs), C.byref(popts),
                                                   B, _capi.stream_ptr()), 'dir_mano_fit_pair')
     return res, pr
 
@@ -436,15 +428,7 @@ def mano_fit_start(tables_lr, init_lr, verts=None, joints=None, joints_conf=None
     hands = len(init_lr)
     assert hands in (1, 2) and len(tables_lr) == hands
     B, dev = init_lr[0].shape[0], init_lr[0].device
-
-    def per_hand(ts, shape, what):
-        ts = [None] * hands if ts is None else list(ts)
-        assert len(ts) == hands
-        for t in ts:
-            if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape and t.device == dev):
-                raise _capi.DirHipError('mano_fit_start: %s must be a contiguous float32 %s tensor on %s' % (what, list(shape), dev))
-        _capi.require_cuda(*ts)
-        return ts
+    per_hand = lambda ts, shape, what: _mano_per_hand('mano_fit_start', hands, dev, ts, shape, what)  # noqa: E731
     init = per_hand(init_lr, (B, 64), 'init')
     tv, tj, cj = per_hand(verts, (B, 778, 3), 'verts'), per_hand(joints, (B, 21, 3), 'joints'), per_hand(joints_conf, (B, 21), 'joints_conf')
     tu, cu, po = per_hand(joint_uv, (B, 21, 2), 'joint_uv'), per_hand(uv_conf, (B, 21), 'uv_conf'), per_hand(para_out, (B, 64), 'para_out')
@@ -483,25 +467,9 @@ def mano_fit_sequence(tables_lr, init_lr, seq_start, verts=None, joints=None, jo
     if not (seq_start.dtype == torch.int32 and seq_start.is_contiguous() and seq_start.dim() == 1 and seq_start.numel() >= 2 and seq_start.device == dev):
         raise _capi.DirHipError('mano_fit_sequence: seq_start must be a contiguous int32 [S+1] tensor on %s' % dev)
     S = seq_start.numel() - 1
-
-    def per_hand(ts, shape, what):
-        ts = [None] * hands if ts is None else list(ts)
-        assert len(ts) == hands
-        for t in ts:
-            if t is not None and not (t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape and t.device == dev):
-                raise _capi.DirHipError('mano_fit_sequence: %s must be a contiguous float32 %s tensor on %s' % (what, list(shape), dev))
-        _capi.require_cuda(*ts)
-        return ts
-    init = per_hand(init_lr, (N, 64), 'init')
-    tv, tj, cj = per_hand(verts, (N, 778, 3), 'verts'), per_hand(joints, (N, 21, 3), 'joints'), per_hand(joints_conf, (N, 21), 'joints_conf')
-    tu, cu = per_hand(joint_uv, (N, 21, 2), 'joint_uv'), per_hand(uv_conf, (N, 21), 'uv_conf')
-    an, st, po = per_hand(anchor, (N, 64), 'anchor'), per_hand(state, (N, _capi.MANO_FIT_STATE), 'state'), per_hand(para_out, (N, 64), 'para_out')
-    sst = per_hand(seq_state, (S, _capi.MANO_FIT_SEQ_STATE), 'seq_state')
-    w = dict(weights or {})
-    if set(w) - set(MANO_FIT_WEIGHTS):
-        raise ValueError('mano_fit_sequence: unknown weights %s' % sorted(set(w) - set(MANO_FIT_WEIGHTS)))
-    opts = _capi.ManoFitOpts(*[float(w.get(k, 0.0)) for k in MANO_FIT_WEIGHTS], (C.c_float * 4)(*[float(v) for v in lr]), float(betas[0]), float(betas[1]),
-                             float(eps), int(iters))
+    res, hs = _mano_fit_hands('mano_fit_sequence', hands, N, dev, init_lr, verts, joints, joints_conf, joint_uv, uv_conf, anchor, state, para_out, outputs)
+    sst = _mano_per_hand('mano_fit_sequence', hands, dev, seq_state, (S, _capi.MANO_FIT_SEQ_STATE), 'seq_state')
+    opts = _mano_fit_opts('mano_fit_sequence', weights, lr, betas, eps, iters)
     host = None if seq_start_host is None else (C.c_int32 * (S + 1))(*[int(v) for v in seq_start_host])
     sopts = _capi.ManoFitSeqOpts(float(smooth[0]), float(smooth[1]), float(smooth[2]), int(bool(share_betas)),
                                  None if host is None else C.cast(host, C.POINTER(C.c_int32)),
@@ -512,18 +480,8 @@ def mano_fit_sequence(tables_lr, init_lr, seq_start, verts=None, joints=None, jo
     if not (work.dtype == torch.uint8 and work.is_contiguous() and work.device == dev):
         raise _capi.DirHipError('mano_fit_sequence: work must be a contiguous uint8 tensor on %s' % dev)
     seq_status = torch.empty(hands, S, dtype=torch.int32, device=dev)
-    res, hs = [], []
-    P = _capi.ptr
-    for h in range(hands):
-        r = {'para': po[h] if po[h] is not None else torch.empty(N, 64, device=dev), 'mse': torch.empty(N, 6, device=dev),
-             'status': torch.empty(N, dtype=torch.int32, device=dev)}
-        if outputs:
-            r.update(verts=torch.empty(N, 778, 3, device=dev), joints=torch.empty(N, 21, 3, device=dev), joint_uv=torch.empty(N, 21, 2, device=dev))
-        hs.append(_capi.ManoFitHand(init[h].data_ptr(), P(an[h]), r['para'].data_ptr(), P(tv[h]), P(tj[h]), P(cj[h]), P(tu[h]), P(cu[h]),
-                                    P(r.get('verts')), P(r.get('joints')), P(r.get('joint_uv')), r['mse'].data_ptr(), r['status'].data_ptr(), P(st[h])))
-        res.append(r)
     with torch.cuda.device(dev):
-        _capi.check(_capi.lib().dir_mano_fit_sequence((_capi.ManoTables * hands)(*tables_lr), (_capi.ManoFitHand * hands)(*hs), C.byref(opts), C.byref(sopts),
+        _capi.check(_capi.lib().dir_mano_fit_sequence((_capi.ManoTables * hands)(*tables_lr), hs, C.byref(opts), C.byref(sopts),
                                                       seq_start.data_ptr(), S, N, hands, seq_status.data_ptr(), work.data_ptr(), work.numel(),
                                                       _capi.stream_ptr()), 'dir_mano_fit_sequence')
     return res, seq_status

@@ -78,12 +78,12 @@ def _term_weights(weights, verts, joints, joint_uv):
     return weights
 
 
-def start_mano(layer_or_tables, init, verts=None, joints=None, joints_conf=None, joint_uv=None, uv_conf=None, weights=None, root=True, cam=True, search=True):
-    """One launch of dir_mano_fit_start: init [B,64] (not written) with its root and camera moved in closed form towards the targets (fit_mano's, each
-    optional).  weights: fit_mano's dict (only w_verts and w_joints are read, as the two 3-D terms' weights against one another).  root / cam: the
-    step may write that group; search: with 2-D targets alone, try the cube's 24 rotations.  -> StartResult(para [B,64], status [B] (bit 0 reflection,
-    bit 1 non-finite input: both passed through; 8 root kept, 16 camera kept), choice [B] (the rotation the search wrote, else -1), info [B,4] (3-D
-    energy before, after; 2-D residual before, after)); lists of two per field for a pair."""
+_Hands = collections.namedtuple('_Hands', 'pair hands ls opt tabs p0 B dev')
+
+
+def _hands(who, layer_or_tables, init):
+    """What start_mano, fit_mano and fit_mano_sequence make of their first two arguments: pair (lists of two were given), hands, ls (an argument as
+    the list per hand), opt (the same for an optional tensor argument, as contiguous float32), the tables, the starts p0, their rows B and device"""
     pair = isinstance(layer_or_tables, (list, tuple))
     hands = 2 if pair else 1
     ls = lambda x: list(x) if pair else [x]  # noqa: E731
@@ -91,8 +91,33 @@ def start_mano(layer_or_tables, init, verts=None, joints=None, joints_conf=None,
     tabs = [_tables(x) for x in ls(layer_or_tables)]
     p0 = [_capi.f32c(t) for t in ls(init)]
     if len(tabs) != hands or len(p0) != hands:
-        raise ValueError('start_mano: a pair takes lists of two')
-    B, dev = p0[0].shape[0], p0[0].device
+        raise ValueError('%s: a pair takes lists of two' % who)
+    return _Hands(pair, hands, ls, opt, tabs, p0, p0[0].shape[0], p0[0].device)
+
+
+def _closed_start(layer_or_tables, init, anchor, verts, joints, joints_conf, joint_uv, uv_conf, weights):
+    """start='closed': start_mano's parameters are the fit's start, and its anchor where none is given.  -> init, anchor"""
+    init = start_mano(layer_or_tables, init, verts, joints, joints_conf, joint_uv, uv_conf, weights).para
+    return init, (init if anchor is None else anchor)
+
+
+def _fit_results(res, p0, st, dev):
+    """functional's per-hand dicts as one FitResult per hand.  res None: the empty batch, nothing was launched.  st: None, or the state per hand"""
+    state = lambda h: None if st is None else st[h]  # noqa: E731
+    if res is None:
+        e = lambda *s: torch.empty((0,) + s, device=dev)  # noqa: E731
+        return [FitResult(p.clone(), e(778, 3), e(21, 3), e(21, 2), e(3), e(3), torch.empty(0, dtype=torch.int32, device=dev), state(h)) for h, p in enumerate(p0)]
+    return [FitResult(r['para'], r.get('verts'), r.get('joints'), r.get('joint_uv'), r['mse'][:, :3], r['mse'][:, 3:], r['status'], state(h))
+            for h, r in enumerate(res)]
+
+
+def start_mano(layer_or_tables, init, verts=None, joints=None, joints_conf=None, joint_uv=None, uv_conf=None, weights=None, root=True, cam=True, search=True):
+    """One launch of dir_mano_fit_start: init [B,64] (not written) with its root and camera moved in closed form towards the targets (fit_mano's, each
+    optional).  weights: fit_mano's dict (only w_verts and w_joints are read, as the two 3-D terms' weights against one another).  root / cam: the
+    step may write that group; search: with 2-D targets alone, try the cube's 24 rotations.  -> StartResult(para [B,64], status [B] (bit 0 reflection,
+    bit 1 non-finite input: both passed through; 8 root kept, 16 camera kept), choice [B] (the rotation the search wrote, else -1), info [B,4] (3-D
+    energy before, after; 2-D residual before, after)); lists of two per field for a pair."""
+    pair, _, _, opt, tabs, p0, B, dev = _hands('start_mano', layer_or_tables, init)
     w = _term_weights(weights, verts, joints, joint_uv)
     if B == 0:
         rs = [StartResult(p.clone(), torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, 4, device=dev))
@@ -116,31 +141,16 @@ def fit_mano(layer_or_tables, init, verts=None, joints=None, joints_conf=None, j
     if start not in (None, 'closed'):
         raise ValueError("fit_mano: start is None or 'closed', got %r" % (start,))
     if start == 'closed':
-        init = start_mano(layer_or_tables, init, verts, joints, joints_conf, joint_uv, uv_conf, weights).para
-        anchor = init if anchor is None else anchor
-    pair = isinstance(layer_or_tables, (list, tuple))
-    hands = 2 if pair else 1
-    ls = lambda x: list(x) if pair else [x]  # noqa: E731
-    opt = lambda x: None if x is None else [None if t is None else _capi.f32c(t) for t in ls(x)]  # noqa: E731
-    tabs = [_tables(x) for x in ls(layer_or_tables)]
-    p0 = [_capi.f32c(t) for t in ls(init)]
-    if len(tabs) != hands or len(p0) != hands:
-        raise ValueError('fit_mano: a pair takes lists of two')
-    B, dev = p0[0].shape[0], p0[0].device
+        init, anchor = _closed_start(layer_or_tables, init, anchor, verts, joints, joints_conf, joint_uv, uv_conf, weights)
+    pair, hands, ls, opt, tabs, p0, B, dev = _hands('fit_mano', layer_or_tables, init)
     weights = _term_weights(weights, verts, joints, joint_uv)
     if state is True:
         state = [new_state(B, dev) for _ in range(hands)]
         state = state if pair else state[0]
     st = None if state is None else ls(state)
-    if B == 0:
-        e = lambda *s: torch.empty((0,) + s, device=dev)  # noqa: E731
-        rs = [FitResult(p.clone(), e(778, 3), e(21, 3), e(21, 2), e(3), e(3), torch.empty(0, dtype=torch.int32, device=dev), None if st is None else st[h])
-              for h, p in enumerate(p0)]
-        return FitResult(*[list(f) for f in zip(*rs)]) if pair else rs[0]
-    res = F.mano_fit(tabs, p0, opt(verts), opt(joints), opt(joints_conf), opt(joint_uv), opt(uv_conf), iters, _lr4(lr), weights, betas, eps,
-                     opt(anchor), st, outputs)
-    rs = [FitResult(r['para'], r.get('verts'), r.get('joints'), r.get('joint_uv'), r['mse'][:, :3], r['mse'][:, 3:], r['status'],
-                    None if st is None else st[h]) for h, r in enumerate(res)]
+    res = None if B == 0 else F.mano_fit(tabs, p0, opt(verts), opt(joints), opt(joints_conf), opt(joint_uv), opt(uv_conf), iters, _lr4(lr), weights, betas, eps,
+                                         opt(anchor), st, outputs)
+    rs = _fit_results(res, p0, st, dev)
     return FitResult(*[list(f) for f in zip(*rs)]) if pair else rs[0]
 
 
@@ -173,17 +183,8 @@ def fit_mano_sequence(layer_or_tables, init, seq_lengths, verts=None, joints=Non
     if start not in ('neutral', 'closed'):
         raise ValueError("fit_mano_sequence: start is 'neutral' or 'closed', got %r" % (start,))
     if start == 'closed':
-        init = start_mano(layer_or_tables, init, verts, joints, joints_conf, joint_uv, uv_conf, weights).para
-        anchor = init if anchor is None else anchor
-    pair = isinstance(layer_or_tables, (list, tuple))
-    hands = 2 if pair else 1
-    ls = lambda x: list(x) if pair else [x]  # noqa: E731
-    opt = lambda x: None if x is None else [None if t is None else _capi.f32c(t) for t in ls(x)]  # noqa: E731
-    tabs = [_tables(x) for x in ls(layer_or_tables)]
-    p0 = [_capi.f32c(t) for t in ls(init)]
-    if len(tabs) != hands or len(p0) != hands:
-        raise ValueError('fit_mano_sequence: a pair takes lists of two')
-    N, dev = p0[0].shape[0], p0[0].device
+        init, anchor = _closed_start(layer_or_tables, init, anchor, verts, joints, joints_conf, joint_uv, uv_conf, weights)
+    pair, hands, ls, opt, tabs, p0, N, dev = _hands('fit_mano_sequence', layer_or_tables, init)
     lengths = [int(n) for n in seq_lengths]
     if any(n < 1 for n in lengths) or sum(lengths) != N:
         raise ValueError('fit_mano_sequence: seq_lengths must be >= 1 and sum to the %d frames, got %s' % (N, lengths[:8]))
@@ -198,16 +199,14 @@ def fit_mano_sequence(layer_or_tables, init, seq_lengths, verts=None, joints=Non
     starts = [0]
     for n in lengths:
         starts.append(starts[-1] + n)
-    if N == 0:
-        e = lambda *s: torch.empty((0,) + s, device=dev)  # noqa: E731
-        rs = [SeqFitResult(p.clone(), e(778, 3), e(21, 3), e(21, 2), e(3), e(3), torch.empty(0, dtype=torch.int32, device=dev), state,
-                           torch.empty(0, dtype=torch.int32, device=dev)) for p in p0]
+    if N == 0:                           # (every hand's state field is the state as given)
+        rs = [SeqFitResult(*f, torch.empty(0, dtype=torch.int32, device=dev)) for f in _fit_results(None, p0, None if state is None else [state] * hands, dev)]
         return SeqFitResult(*[list(f) for f in zip(*rs)]) if pair else rs[0]
     res, seq_status = F.mano_fit_sequence(tabs, p0, torch.tensor(starts, dtype=torch.int32).to(dev), opt(verts), opt(joints), opt(joints_conf), opt(joint_uv),
                                           opt(uv_conf), iters, _lr4(lr), weights, [float(smooth.get(k, 0.0)) for k in ('root', 'pca', 'cam')], share_betas, betas,
                                           eps, opt(anchor), fr, sq, outputs, work=work, seq_start_host=starts)
-    rs = [SeqFitResult(r['para'], r.get('verts'), r.get('joints'), r.get('joint_uv'), r['mse'][:, :3], r['mse'][:, 3:], r['status'],
-                       None if state is None else SeqState(fr[h], sq[h]), seq_status[h]) for h, r in enumerate(res)]
+    st = None if state is None else [SeqState(fr[h], sq[h]) for h in range(hands)]
+    rs = [SeqFitResult(*f, seq_status[h]) for h, f in enumerate(_fit_results(res, p0, st, dev))]
     if not pair:
         return rs[0]
     out = SeqFitResult(*[list(f) for f in zip(*rs)])
@@ -276,8 +275,7 @@ def fit_mano_pair(layers_or_tables, init, offset0, *, radii=None, offset_target=
     if weights is not None and set(weights) - set(F.MANO_FIT_WEIGHTS) - set(F.MANO_FIT_PAIR_WEIGHTS):
         raise ValueError('fit_mano_pair: unknown weights %s' % sorted(set(weights) - set(F.MANO_FIT_WEIGHTS) - set(F.MANO_FIT_PAIR_WEIGHTS)))
     if start == 'closed':
-        init = start_mano(list(layers_or_tables), list(init), verts, joints, joints_conf, joint_uv, uv_conf, term_w).para
-        anchor = init if anchor is None else anchor
+        init, anchor = _closed_start(list(layers_or_tables), list(init), anchor, verts, joints, joints_conf, joint_uv, uv_conf, term_w)
     opt = lambda x: None if x is None else [None if t is None else _capi.f32c(t) for t in x]  # noqa: E731
     one = lambda t: None if t is None else _capi.f32c(t)  # noqa: E731
     tabs = [_tables(x) for x in layers_or_tables]
@@ -297,12 +295,9 @@ def fit_mano_pair(layers_or_tables, init, offset0, *, radii=None, offset_target=
     st, ost = (None, None) if state is None else (list(state[0]), state[1])
     o0 = _capi.f32c(offset0)
     if B == 0:
-        e = lambda *s: torch.empty((0,) + s, device=dev)  # noqa: E731
-        ei = torch.empty(0, dtype=torch.int32, device=dev)
-        rs = [FitResult(p.clone(), e(778, 3), e(21, 3), e(21, 2), e(3), e(3), ei.clone(), None if st is None else st[h]) for h, p in enumerate(p0)]
-        return PairFitResult(*[list(f) for f in zip(*rs)], o0.clone(), e(4), ei, ost)
-    res, pr = F.mano_fit_pair(tabs, p0, o0, [_capi.f32c(r) for r in radii], opt(verts), opt(joints), opt(joints_conf), opt(joint_uv), opt(uv_conf), iters, lr4, lr_o,
-                              term_w, pair_w, one(offset_target), one(offset_conf), one(offset_anchor), betas, eps, opt(anchor), st, ost, outputs)
-    rs = [FitResult(r['para'], r.get('verts'), r.get('joints'), r.get('joint_uv'), r['mse'][:, :3], r['mse'][:, 3:], r['status'],
-                    None if st is None else st[h]) for h, r in enumerate(res)]
-    return PairFitResult(*[list(f) for f in zip(*rs)], pr['offset'], pr['col'], pr['pair_status'], ost)
+        pr = {'offset': o0.clone(), 'col': torch.empty(0, 4, device=dev), 'pair_status': torch.empty(0, dtype=torch.int32, device=dev)}
+        res = None
+    else:
+        res, pr = F.mano_fit_pair(tabs, p0, o0, [_capi.f32c(r) for r in radii], opt(verts), opt(joints), opt(joints_conf), opt(joint_uv), opt(uv_conf), iters, lr4,
+                                  lr_o, term_w, pair_w, one(offset_target), one(offset_conf), one(offset_anchor), betas, eps, opt(anchor), st, ost, outputs)
+    return PairFitResult(*[list(f) for f in zip(*_fit_results(res, p0, st, dev))], pr['offset'], pr['col'], pr['pair_status'], ost)
