@@ -20,19 +20,13 @@
 // A half's residual registers are re-requested for the next tile as soon as they have been copied to T (a tile of lead time);
 // all global accesses are unconditional (clamped addresses, zero-select at the LDS write) so that the compiler's in-order vmcnt
 // accounting stays exact and no wait covers more than it needs.
-#include "conv_common.h"
-
-#ifndef DIR_BNECK_RES16
-#define DIR_BNECK_RES16 1      // A/B switch: the residual as 16-byte chunks + v_permlane32_swap (1) or as 8-byte pieces in the accumulator layout (0)
-#endif
+#include "chain_common.h"
 
 namespace dir {
 namespace {
 
-using convk::bf16_t;
+using namespace chain;
 using convk::f16s_t;
-using convk::Half;
-using convk::f32x16;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 constexpr int TH = 8, TW = 16, NPX = TH * TW;            // tile: 8 rows x 16 cols = 128 pixels, pixel P = row * 16 + col
@@ -52,11 +46,6 @@ struct ChainArgs {
     int B, H, W, tiles_x, tiles_y, ntiles;
     int decim;                                            // 1: only the pixels with even y and even x leave, as out [B][H/2][W/2][256]
 };
-
-template <typename H> __device__ __forceinline__ void unpack4(uint2 v, float (&f)[4]) {
-    convk::unpack2<H>(v.x, f[0], f[1]);
-    convk::unpack2<H>(v.y, f[2], f[3]);
-}
 
 // N2: output channels of the fused next conv1 (0 = none, 64 = next layer1 block, 128 = first block of layer2)
 // H: the 16-bit storage kind (bf16_t | f16s_t = DIR_DT_BF16 | DIR_DT_F16) of every tensor, weight and LDS tile
@@ -98,13 +87,8 @@ __global__ __launch_bounds__(NTHR, 1) void bneck_chain_kernel(ChainArgs a) {
         for (int s = 0; s < 8; ++s) w1f[s] = *reinterpret_cast<const convk::u32x4*>(a.w1n + (16 * ct + l16) * 256 + 32 * s + 8 * g);
     }
 
-    // XCD-aware tile order: the 32 workgroups of one XCD walk one contiguous range of tiles (halo rows hit the same L2)
-    const int nblk = gridDim.x;
     int t0, tstep, tend;
-    if ((nblk & 7) == 0 && a.ntiles % 8 == 0) {
-        const int per = a.ntiles >> 3;
-        t0 = (blockIdx.x & 7) * per + (blockIdx.x >> 3); tstep = nblk >> 3; tend = ((blockIdx.x & 7) + 1) * per;
-    } else { t0 = blockIdx.x; tstep = nblk; tend = a.ntiles; }
+    xcd_tile_range(gridDim.x, blockIdx.x, a.ntiles, t0, tstep, tend);
 
     // ---- halo patch prefetch: chunk e = tid + 512 i -> patch pixel e >> 3, 16-byte channel chunk e & 7
     uint4 pre[NPRE];
@@ -160,15 +144,10 @@ __global__ __launch_bounds__(NTHR, 1) void bneck_chain_kernel(ChainArgs a) {
 
     // Block output leaves through the T tile ([64 pixels][256 channels] bf16 per half) with COALESCED 16-byte stores: chunk
     // c = tid + 512 i of a half = pixel c >> 5, channel chunk c & 31, i.e. two whole 512-byte pixels per wave instruction.  The
-    // residual is read straight into the epilogue-B register layout (pixel 64 mg + 32 j + l32, channels 32 wave + 8 q + 4 h .. +4;
-    // 8-byte pieces): measured, the extra LDS round trip + barrier of a coalesced residual costs more than it saves.
-    // Since round 3 as 16-byte chunks (lane half h: channels 16 jj + 8 h .. + 8), swapped into the accumulator layout with
-    // v_permlane32_swap where they are used: half the load instructions (tail.hip, same change).
-#if DIR_BNECK_RES16
+    // residual is read straight into registers (pixel 64 mg + 32 j + l32, channels 32 wave ..): measured, the extra LDS round trip + barrier
+    // of a coalesced residual costs more than it saves.  As 16-byte chunks, turned into the epilogue-B layout where they are used
+    // (chain_common.h: res16_fetch / res16_take): half the load instructions of 8-byte pieces in that layout.
     uint4 xr[2][2][2];
-#else
-    uint2 xr[2][2][4];
-#endif
     auto out_ptr = [&](int mg, int i, int rb, int ry0, int rx0) {
         const int c = tid + NTHR * i, P = 64 * mg + (c >> 5);
         return a.out + (((long long)rb * a.H + ry0 + (P >> 4)) * a.W + rx0 + (P & 15)) * 256 + (c & 31) * 8;
@@ -187,15 +166,7 @@ __global__ __launch_bounds__(NTHR, 1) void bneck_chain_kernel(ChainArgs a) {
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const int P = 64 * mg + 32 * j + l32;
-#if DIR_BNECK_RES16
-                    const bf16_t* rp = a.res + (((long long)b * a.H + y0 + (P >> 4)) * a.W + x0 + (P & 15)) * 256 + 32 * wave + 8 * h;
-#pragma unroll
-                    for (int jj = 0; jj < 2; ++jj) xr[mg][j][jj] = *reinterpret_cast<const uint4*>(rp + 16 * jj);
-#else
-                    const bf16_t* rp = a.res + (((long long)b * a.H + y0 + (P >> 4)) * a.W + x0 + (P & 15)) * 256 + 32 * wave + 4 * h;
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) xr[mg][j][q] = *reinterpret_cast<const uint2*>(rp + 8 * q);
-#endif
+                    res16_fetch(a.res + (((long long)b * a.H + y0 + (P >> 4)) * a.W + x0 + (P & 15)) * 256 + 32 * wave + 8 * h, xr[mg][j]);
                 }
         }
 
@@ -235,10 +206,7 @@ __global__ __launch_bounds__(NTHR, 1) void bneck_chain_kernel(ChainArgs a) {
                 const int c0 = 32 * nt + 8 * q + 4 * h;
                 const float4 sc = *reinterpret_cast<const float4*>(s_ss + c0);
                 const float4 sh = *reinterpret_cast<const float4*>(s_ss + 64 + c0);
-                uint2 o;
-                o.x = Half<H>::pack2_relu(fmaf(acc[4 * q], sc.x, sh.x), fmaf(acc[4 * q + 1], sc.y, sh.y));
-                o.y = Half<H>::pack2_relu(fmaf(acc[4 * q + 2], sc.z, sh.z), fmaf(acc[4 * q + 3], sc.w, sh.w));
-                *reinterpret_cast<uint2*>(s_y2 + (32 * mt + l32) * PPITCH + c0 * 2) = o;
+                *reinterpret_cast<uint2*>(s_y2 + (32 * mt + l32) * PPITCH + c0 * 2) = bn_relu4<H>(acc, q, sc, sh);
             }
         }
         __syncthreads();                                                      // y2 complete; the patch is free
@@ -286,25 +254,14 @@ __global__ __launch_bounds__(NTHR, 1) void bneck_chain_kernel(ChainArgs a) {
                     char* tp = s_t + (32 * j + l32) * TPITCH + c0 * 2;
                     const float4 sc = *reinterpret_cast<const float4*>(s_ss + 128 + c0);
                     const float4 sh = *reinterpret_cast<const float4*>(s_ss + 384 + c0);
-                    float v[4] = {fmaf(accb[j][4 * q], sc.x, sh.x), fmaf(accb[j][4 * q + 1], sc.y, sh.y),
-                                  fmaf(accb[j][4 * q + 2], sc.z, sh.z), fmaf(accb[j][4 * q + 3], sc.w, sh.w)};
                     if constexpr (HAS_RES) {
-                        float rv[4];
-#if DIR_BNECK_RES16
-                        const uint4 c = xr[mg][j][q >> 1];            // (q even, q odd) = swap(lower 8 bytes, upper 8 bytes) with the partner lane
-                        const auto sx = __builtin_amdgcn_permlane32_swap(c.x, c.z, false, false);
-                        const auto sy = __builtin_amdgcn_permlane32_swap(c.y, c.w, false, false);
-                        unpack4<H>(make_uint2(sx[q & 1], sy[q & 1]), rv);
-#else
-                        unpack4<H>(xr[mg][j][q], rv);
-#endif
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) v[e] += rv[e];
+                        float v[4], rv[4];
+                        bn4(accb[j], q, sc, sh, v);
+                        res16_take<H>(xr[mg][j], q, rv);
+                        *reinterpret_cast<uint2*>(tp) = add_relu4<H>(v, rv);
+                    } else {
+                        *reinterpret_cast<uint2*>(tp) = bn_relu4<H>(accb[j], q, sc, sh);
                     }
-                    uint2 o;
-                    o.x = Half<H>::pack2_relu(v[0], v[1]);
-                    o.y = Half<H>::pack2_relu(v[2], v[3]);
-                    *reinterpret_cast<uint2*>(tp) = o;
                 }
             }
             __syncthreads();                                                  // T = this half of the block output
@@ -344,10 +301,7 @@ __global__ __launch_bounds__(NTHR, 1) void bneck_chain_kernel(ChainArgs a) {
 #pragma unroll
                 for (int u = 0; u < NPT; ++u) {
                     const int P = 64 * mg + 16 * (pt0 + u) + l16;
-                    uint2 o;
-                    o.x = Half<H>::pack2_relu(fmaf(accc[u][0], sc.x, sh.x), fmaf(accc[u][1], sc.y, sh.y));
-                    o.y = Half<H>::pack2_relu(fmaf(accc[u][2], sc.z, sh.z), fmaf(accc[u][3], sc.w, sh.w));
-                    *reinterpret_cast<uint2*>(a.y1n + (((long long)b * a.H + y0 + (P >> 4)) * a.W + x0 + (P & 15)) * N2 + c0) = o;
+                    *reinterpret_cast<uint2*>(a.y1n + (((long long)b * a.H + y0 + (P >> 4)) * a.W + x0 + (P & 15)) * N2 + c0) = bn_relu4<H>(accc[u], 0, sc, sh);
                 }
             }
             if (mg == 0) __syncthreads();                                     // T free for the second half
@@ -381,12 +335,7 @@ extern "C" int dir_bottleneck_chain_forward(const dir_bneck_chain_params* p, con
     const long long nt = (long long)B * a.tiles_x * a.tiles_y;
     DIR_REQUIRE(nt < (1ll << 31) && (long long)B * H * W * 256 < (1ll << 40), "dir_bottleneck_chain_forward: too large");
     a.ntiles = (int)nt;
-    static int num_cu = 0;
-    if (!num_cu) {
-        int dev = 0; hipDeviceProp_t pr;
-        num_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256;
-    }
-    const int grid = (int)(nt < num_cu ? nt : num_cu);
+    const int grid = persistent_grid(nt);
     hipStream_t s = (hipStream_t)stream;
     const bool res = residual != nullptr;
     const int n2 = next ? p->n_next : 0;

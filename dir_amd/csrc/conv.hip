@@ -712,12 +712,7 @@ static int conv_forward(const dir_conv_desc* d, const void* x, const void* w, co
                      (residual == nullptr || (res_cs % epo == 0 && d->res_coff % epo == 0));
     if (vec) a.flags |= 4;
     DIR_REQUIRE(a.out_split_scale == 0.f || vec, "dir_conv2d_forward: out_split_scale needs 16-byte aligned output / residual rows");
-    static int num_cu = 0;
-    if (num_cu == 0) {
-        int dev = 0;
-        hipDeviceProp_t p;
-        num_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) ? p.multiProcessorCount : 256;
-    }
+    const int num_cu = dir::num_cus();
     a.splits = 0; a.ws_part = nullptr; a.ws_cnt = nullptr;
     a.st_p1 = st_p1; a.st_p2 = st_p2;
     stats_rows_launched = 0;

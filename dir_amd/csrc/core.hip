@@ -15,6 +15,17 @@ void set_error(const char* fmt, ...) {
 }  // namespace dir
 
 namespace dir {
+int num_cus() {
+    static const int n = [] {
+        int dev = 0;
+        hipDeviceProp_t p;
+        return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) ? p.multiProcessorCount : 256;
+    }();
+    return n;
+}
+}  // namespace dir
+
+namespace dir {
 long long* stamps_begin(const char* kernel) {
     const char* e = getenv("DIR_STAMPS");
     if (!e || strcmp(e, kernel) != 0) return nullptr;

@@ -38,6 +38,14 @@ inline int check_launch(const char* what) {
         }                               \
     } while (0)
 
+// Compute units of the device current at the first call, asked from the runtime once per process (one process drives one GPU here); 256 if the
+// query fails.  persistent_grid: the grid of a persistent kernel -- one workgroup per tile up to per_cu workgroups per CU.
+int num_cus();
+inline int persistent_grid(long long ntiles, int per_cu = 1) {
+    const long long cap = (long long)per_cu * num_cus();
+    return (int)(ntiles < cap ? ntiles : cap);
+}
+
 // Tuning aid shared by the latency-bound token kernels: with DIR_STAMPS=<kernel name> in the environment the launcher passes a
 // device buffer and thread 0 of workgroup 0 writes s_memtime at every phase boundary; the launcher then prints the phase
 // durations (ticks of the shader clock counter) to stderr.  NULL (the normal case) costs one uniform branch per stamp.

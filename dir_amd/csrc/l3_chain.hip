@@ -23,15 +23,13 @@
 // 16 ks + 8 h .. + 8); with N2 = 0 conv3 has conv.hip's, because the launch it replaces is then a convolution.  Either way the output is
 // bit-identical to the launches replaced.
 // No flags, no counters, no dependence between workgroups.
-#include "conv_common.h"
+#include "chain_common.h"
 
 namespace dir {
 namespace {
 
-using convk::bf16_t;
+using namespace chain;
 using convk::f16s_t;
-using convk::f32x16;
-using convk::Half;
 
 constexpr int P = 256, C4 = 1024;      // planes, block width
 constexpr int TM = 64;                 // pixels per tile: 4 rows x 16 columns
@@ -54,13 +52,6 @@ struct L3Args {
     int H, tiles_per_img, ntiles;
 };
 
-template <typename H> __device__ __forceinline__ void unpack4(uint2 v, float (&f)[4]) {
-    convk::unpack2<H>(v.x, f[0], f[1]);
-    convk::unpack2<H>(v.y, f[2], f[3]);
-}
-
-template <int V> struct IC : std::integral_constant<int, V> {};
-
 // N2: output channels of the fused next conv1 (256), or 0: none (the layer's last block)
 template <int N2, typename H>
 __global__ __launch_bounds__(NTHR, 1) void l3_chain_kernel(L3Args a) {
@@ -78,13 +69,8 @@ __global__ __launch_bounds__(NTHR, 1) void l3_chain_kernel(L3Args a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l32 = lane & 31, h = lane >> 5;
 
-    // XCD-aware tile order (res_chain.hip): the workgroups of one XCD walk one contiguous range of tiles, so halo rows hit the same L2
-    const int nblk = gridDim.x;
     int t0, tstep, tend;
-    if ((nblk & 7) == 0 && a.ntiles % 8 == 0) {
-        const int per = a.ntiles >> 3;
-        t0 = (blockIdx.x & 7) * per + (blockIdx.x >> 3); tstep = nblk >> 3; tend = ((blockIdx.x & 7) + 1) * per;
-    } else { t0 = blockIdx.x; tstep = nblk; tend = a.ntiles; }
+    xcd_tile_range(gridDim.x, blockIdx.x, a.ntiles, t0, tstep, tend);
     if (t0 >= tend) return;
 
     // ---- weight stream of this wave: fragment f of a tile at wstream[(wave * NF + f) * 64 + lane]
@@ -108,17 +94,14 @@ __global__ __launch_bounds__(NTHR, 1) void l3_chain_kernel(L3Args a) {
     const float* const s_sc3 = s_ss + 2 * P;
     const float* const s_sh3 = s_ss + 2 * P + C4;
 
-    // ---- identity rows of a unit in the epilogue-B layout (tail.hip): 16-byte chunks, lane half h takes channels 16 j + 8 h .. + 8 of each
-    //      32-channel block; turned into the accumulator layout at the point of use (v_permlane32_swap)
+    // ---- identity rows of a unit as 16-byte chunks, turned into the epilogue-B layout where they are used (chain_common.h: res16_fetch / res16_take)
     uint4 xr[2][2][2];
     auto res_fetch = [&](int tile, int half) {
 #pragma unroll
         for (int pb = 0; pb < 2; ++pb) {
             const bf16_t* rp = a.res + ((long long)tile * TM + 32 * pb + l32) * C4 + half * HC + 64 * wave + 8 * h;
 #pragma unroll
-            for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) xr[cb][pb][j] = *reinterpret_cast<const uint4*>(rp + 32 * cb + 16 * j);
+            for (int cb = 0; cb < 2; ++cb) res16_fetch(rp + 32 * cb, xr[cb][pb]);
         }
     };
 
@@ -203,10 +186,7 @@ __global__ __launch_bounds__(NTHR, 1) void l3_chain_kernel(L3Args a) {
                     const int c0 = 32 * wave + 8 * q + 4 * h;
                     const float4 sc = *reinterpret_cast<const float4*>(s_ss + c0);
                     const float4 sh = *reinterpret_cast<const float4*>(s_ss + P + c0);
-                    uint2 o;
-                    o.x = Half<H>::pack2_relu(fmaf(acc[j][4 * q], sc.x, sh.x), fmaf(acc[j][4 * q + 1], sc.y, sh.y));
-                    o.y = Half<H>::pack2_relu(fmaf(acc[j][4 * q + 2], sc.z, sh.z), fmaf(acc[j][4 * q + 3], sc.w, sh.w));
-                    *reinterpret_cast<uint2*>(s_y2 + (32 * j + l32) * YPITCH + c0 * 2) = o;
+                    *reinterpret_cast<uint2*>(s_y2 + (32 * j + l32) * YPITCH + c0 * 2) = bn_relu4<H>(acc[j], q, sc, sh);
                 }
         }
         __syncthreads();                                 // y2 complete; every wave is done with the patch: T may take its place
@@ -248,44 +228,13 @@ __global__ __launch_bounds__(NTHR, 1) void l3_chain_kernel(L3Args a) {
                                   for (int pb = 0; pb < 2; ++pb) accb[pb] = Half<H>::mfma32(ring[slot][I], bop[set][pb], accb[pb]);
                                   if constexpr (ks == 15) {
                                       // ---- epilogue B of this channel block -> T: bn3 + identity + ReLU, rounded
-#pragma unroll
-                                      for (int q = 0; q < 4; ++q) {
-                                          const int cl = 64 * wave + 32 * cb + 8 * q + 4 * h;                  // channel inside the half
-                                          const float4 sc = *reinterpret_cast<const float4*>(s_sc3 + hf * HC + cl);
-                                          const float4 sh = *reinterpret_cast<const float4*>(s_sh3 + hf * HC + cl);
-#pragma unroll
-                                          for (int pb = 0; pb < 2; ++pb) {
-                                              float v[4] = {fmaf(accb[pb][4 * q], sc.x, sh.x), fmaf(accb[pb][4 * q + 1], sc.y, sh.y),
-                                                            fmaf(accb[pb][4 * q + 2], sc.z, sh.z), fmaf(accb[pb][4 * q + 3], sc.w, sh.w)};
-                                              float rv[4];
-                                              {   // (q even, q odd) = swap(lower 8 bytes, upper 8 bytes) of chunk q / 2, dword by dword
-                                                  const uint4 c = xr[cb][pb][q >> 1];
-                                                  const auto sx = __builtin_amdgcn_permlane32_swap(c.x, c.z, false, false);
-                                                  const auto sy = __builtin_amdgcn_permlane32_swap(c.y, c.w, false, false);
-                                                  unpack4<H>(make_uint2(sx[q & 1], sy[q & 1]), rv);
-                                              }
-#pragma unroll
-                                              for (int e = 0; e < 4; ++e) v[e] += rv[e];
-                                              uint2 o;
-                                              o.x = Half<H>::pack2_relu(v[0], v[1]);
-                                              o.y = Half<H>::pack2_relu(v[2], v[3]);
-                                              *reinterpret_cast<uint2*>(s_t + (32 * pb + l32) * TPITCH + cl * 2) = o;
-                                          }
-                                          __builtin_amdgcn_sched_barrier(0);
-                                      }
+                                      epilogue_b<H, TPITCH>(accb, xr[cb], s_sc3 + hf * HC, s_sh3 + hf * HC, s_t, 64 * wave + 32 * cb, l32, h);
                                   }
                                   if constexpr (f == NBF - 1) {
                                       __syncthreads();                               // T = this half of the block output
                                       if constexpr (NEXT) act_read(IC<NBF>{}, IC<set ^ 1>{});
                                       if constexpr (!last_half) res_fetch(t, hf + 1);     // into the registers just consumed
-                                      // block output: coalesced 16-byte stores from T (chunk c = pixel c >> 6, 16-byte chunk c & 63)
-#pragma unroll
-                                      for (int i = 0; i < TM * (HC / 8) / NTHR; ++i) {
-                                          const int c = tid + NTHR * i;
-                                          *reinterpret_cast<uint4*>(a.out + ((long long)t * TM + (c >> 6)) * C4 + hf * HC + (c & 63) * 8) =
-                                              *reinterpret_cast<const uint4*>(s_t + (c >> 6) * TPITCH + (c & 63) * 16);
-                                          if (i & 1) __builtin_amdgcn_sched_barrier(0);
-                                      }
+                                      store_t_to_out<NTHR, TM, HC, TPITCH>(s_t, a.out, C4, t, hf, tid);
                                   }
                               } else {
                                   // ---- C. next conv1 over this half's 512 input channels
@@ -300,7 +249,8 @@ __global__ __launch_bounds__(NTHR, 1) void l3_chain_kernel(L3Args a) {
                  ...);
             }(std::make_integer_sequence<int, NGU>{});
             if constexpr (NEXT && last_half) {
-                // ---- epilogue C: bn1 + ReLU -> next y1 (tail.hip: the identity fetch's swap in reverse, one 16-byte store per j)
+                // ---- epilogue C: bn1 + ReLU -> next y1, one 16-byte store per j (tail.hip's, kept in place in both: as one shared function it moved
+                //      tail_chain_kernel<256, 256>'s register allocation)
                 const float* const s_sc1 = s_ss + 2 * P + 2 * C4;
 #pragma unroll
                 for (int pb = 0; pb < 2; ++pb) {
@@ -310,15 +260,9 @@ __global__ __launch_bounds__(NTHR, 1) void l3_chain_kernel(L3Args a) {
                         const int c0 = 32 * wave + 8 * q + 4 * h;
                         const float4 sc = *reinterpret_cast<const float4*>(s_sc1 + c0);
                         const float4 sh = *reinterpret_cast<const float4*>(s_sc1 + N2 + c0);
-                        o[q].x = Half<H>::pack2_relu(fmaf(accc[pb][4 * q], sc.x, sh.x), fmaf(accc[pb][4 * q + 1], sc.y, sh.y));
-                        o[q].y = Half<H>::pack2_relu(fmaf(accc[pb][4 * q + 2], sc.z, sh.z), fmaf(accc[pb][4 * q + 3], sc.w, sh.w));
+                        o[q] = bn_relu4<H>(accc[pb], q, sc, sh);
                     }
-#pragma unroll
-                    for (int j = 0; j < 2; ++j) {
-                        const auto dx = __builtin_amdgcn_permlane32_swap(o[2 * j].x, o[2 * j + 1].x, false, false);
-                        const auto dy = __builtin_amdgcn_permlane32_swap(o[2 * j].y, o[2 * j + 1].y, false, false);
-                        *reinterpret_cast<uint4*>(a.y1n + ((long long)t * TM + 32 * pb + l32) * N2 + 32 * wave + 16 * j + 8 * h) = make_uint4(dx[0], dy[0], dx[1], dy[1]);
-                    }
+                    store16_swapped(o, a.y1n + ((long long)t * TM + 32 * pb + l32) * N2 + 32 * wave + 8 * h);
                 }
             }
             __syncthreads();                             // T (and after the last half y2) is free
@@ -352,12 +296,7 @@ extern "C" int dir_bottleneck_block_forward(const dir_bneck_block_params* p, con
     a.wstream = (const uint4*)p->wstream;
     a.sc2 = p->scale2; a.sh2 = p->shift2; a.sc3 = p->scale3; a.sh3 = p->shift3; a.sc1n = p->scale1n; a.sh1n = p->shift1n;
     a.H = H; a.tiles_per_img = H / 4; a.ntiles = B * (H / 4);
-    static int num_cu = 0;
-    if (!num_cu) {
-        int dev = 0; hipDeviceProp_t pr;
-        num_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256;
-    }
-    const int grid = a.ntiles < num_cu ? a.ntiles : num_cu;
+    const int grid = persistent_grid(a.ntiles);
     hipStream_t s = (hipStream_t)stream;
     const bool f16 = p->dtype == DIR_DT_F16;
     if (p->n_next == 256) {

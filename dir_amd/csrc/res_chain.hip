@@ -1,6 +1,6 @@
 // dir_residual_chain_forward: one hourglass Residual block (Cin = 512, mid = 128, Cout = 256, stride 1) in ONE kernel (16-bit storage)
 //   models/backbone/hourglass.py:33-70   out = conv3(relu(bn3(conv2(relu(bn2(conv1(relu(bn1(x)))))))) + skip_layer(x)
-// Unfused the block is three launches (dir_amd/engine.py::ResidualOp): c1 1x1 with the pre-activation, c2 3x3, and conv3 + skip_layer as one GEMM
+// Unfused the block is three launches (dir_amd/engine/decoder.py::ResidualOp): c1 1x1 with the pre-activation, c2 3x3, and conv3 + skip_layer as one GEMM
 // over two K ranges.  On a 32x32 map at B = 64 they move 235 MB -- x twice, y1 and y2 written and read back -- for 101 MB of x + out.  Here y1 and
 // y2 never leave the CU.
 //
@@ -16,21 +16,19 @@
 //      into the destination's channel slice.
 // The weights (w1 128 KB, w2 288 KB, w3 | skip 320 KB) do not fit a CU: every wave streams its MFMA A fragments from L2 in the order it consumes
 // them -- ONE stream of 36 steps per tile (8 + 18 + 10; a step = 4 k-steps of 16 channels = 4 fragments of 1 KB) through a register ring two steps
-// ahead, running across the phase boundaries and into the next tile.  The host packs them once (dir_amd/engine.py::pack_as_weights with A = 1).
+// ahead, running across the phase boundaries and into the next tile.  The host packs them once (dir_amd/packing.py::pack_as_weights with A = 1).
 // Every global load is unconditional (clamped address): a load inside a branch makes hipcc wait for everything at the join (stream.hip).
 //
 // fp32 accumulation in the K order and k-slot assignment of conv.hip (stream.hip's header): 64-channel slab outer, taps inner; MFMA ks of a slab
 // multiplies channels 8 ks .. + 8 in lanes 0-31 and 32 + 8 ks .. + 8 in lanes 32-63; epilogues fmaf(acc, scale, shift) -> round -> ReLU.  The sums
 // are the same fp32 chains as the three launches', the output is bit-identical.
-#include "conv_common.h"
+#include "chain_common.h"
 
 namespace dir {
 namespace {
 
-using convk::bf16_t;
+using namespace chain;
 using convk::f16s_t;
-using convk::f32x16;
-using convk::Half;
 
 constexpr int RC_CIN = 512, RC_MID = 128, RC_COUT = 256;
 constexpr int TH = 8, TW = 16, NPX = TH * TW;              // tile: 128 pixels, P = row * 16 + col
@@ -96,16 +94,11 @@ __global__ __launch_bounds__(NTHR, 1) void res_chain_kernel(ResArgs a) {
         }
     };
 
-    // XCD-aware tile order (bneck.hip): the workgroups of one XCD walk one contiguous range of tiles -- whole images, so halo rows hit the same L2
-    const int nblk = gridDim.x;
     int t0, tstep, tend;
-    if ((nblk & 7) == 0 && a.ntiles % 8 == 0) {
-        const int per = a.ntiles >> 3;
-        t0 = (blockIdx.x & 7) * per + (blockIdx.x >> 3); tstep = nblk >> 3; tend = ((blockIdx.x & 7) + 1) * per;
-    } else { t0 = blockIdx.x; tstep = nblk; tend = a.ntiles; }
+    xcd_tile_range(gridDim.x, blockIdx.x, a.ntiles, t0, tstep, tend);
 
-    wload(std::integral_constant<int, 0>{});
-    wload(std::integral_constant<int, 1>{});
+    wload(IC<0>{});
+    wload(IC<1>{});
     __syncthreads();                                                              // s_pre, s_ss
 
     for (int t = t0; t < tend; t += tstep) {
@@ -160,8 +153,8 @@ __global__ __launch_bounds__(NTHR, 1) void res_chain_kernel(ResArgs a) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) *reinterpret_cast<uint4*>(s_x[buf] + ((tid + NTHR * i) >> 3) * XPITCH + cc * 16) = xa[decltype(Set)::value][i];
         };
-        using I0 = std::integral_constant<int, 0>;
-        using I1 = std::integral_constant<int, 1>;
+        using I0 = IC<0>;
+        using I1 = IC<1>;
 
         // ================================================================ A. c1 on the patch: 32 channels x 96 patch positions per wave
         loadA(I0{}, 0);
@@ -180,7 +173,7 @@ __global__ __launch_bounds__(NTHR, 1) void res_chain_kernel(ResArgs a) {
                 (([&] {
                      constexpr int c = Cs;
                      __builtin_amdgcn_sched_barrier(0);                          // a step's reads stay inside the step (unrolled, they were hoisted until the registers ran out)
-                     wload(std::integral_constant<int, c + 2>{});
+                     wload(IC<c + 2>{});
                      const char* bp = bA + (c & 1) * XBUF;
                      uint4 bv[2][3];                                              // the pixels' channels (MFMA B operands), read a k-step ahead
 #pragma unroll
@@ -196,8 +189,8 @@ __global__ __launch_bounds__(NTHR, 1) void res_chain_kernel(ResArgs a) {
                          for (int j = 0; j < 3; ++j) acc[j] = Half<H>::mfma32(wr[c % 3][ks], bv[ks & 1][j], acc[j]);
                      }
                      if constexpr (c + 1 < 8) {                                   // chunk c + 1 -> the other buffer (free since the last barrier); c + 3 on its way
-                         storeA(std::integral_constant<int, (c + 1) & 1>{}, c + 1, (c + 1) & 1);
-                         if constexpr (c + 3 < 8) loadA(std::integral_constant<int, (c + 1) & 1>{}, c + 3);
+                         storeA(IC<(c + 1) & 1>{}, c + 1, (c + 1) & 1);
+                         if constexpr (c + 3 < 8) loadA(IC<(c + 1) & 1>{}, c + 3);
                      } else {                                                     // the tile's own pixels for phase C, chunks 0 and 1: in flight during phase B
                          loadC(I0{}, 0);
                          loadC(I1{}, 1);
@@ -218,9 +211,7 @@ __global__ __launch_bounds__(NTHR, 1) void res_chain_kernel(ResArgs a) {
                         const int c0 = 32 * cb + 8 * q + 4 * h;
                         const float4 sc = *reinterpret_cast<const float4*>(s_ss + c0);
                         const float4 sh = *reinterpret_cast<const float4*>(s_ss + RC_MID + c0);
-                        uint2 o;
-                        o.x = Half<H>::pack2_relu(fmaf(acc[j][4 * q], sc.x, sh.x), fmaf(acc[j][4 * q + 1], sc.y, sh.y));
-                        o.y = Half<H>::pack2_relu(fmaf(acc[j][4 * q + 2], sc.z, sh.z), fmaf(acc[j][4 * q + 3], sc.w, sh.w));
+                        uint2 o = bn_relu4<H>(acc[j], q, sc, sh);
                         if (!in) o = make_uint2(0u, 0u);
                         *reinterpret_cast<uint2*>(s_y1 + pr * Y1ROW + pc * YPITCH + c0 * 2) = o;
                     }
@@ -244,16 +235,16 @@ __global__ __launch_bounds__(NTHR, 1) void res_chain_kernel(ResArgs a) {
 #pragma unroll
                 for (int j = 0; j < 2; ++j) bv[i & 1][j] = *reinterpret_cast<const uint4*>(bB + (ky + 2 * j) * Y1ROW + kx * YPITCH + slab * 128 + 16 * ks);
             };
-            bread(std::integral_constant<int, 0>{});
+            bread(IC<0>{});
             [&]<int... Ss>(std::integer_sequence<int, Ss...>) {
                 (([&] {
                      constexpr int s = Ss;                                        // step = slab * 9 + tap: 64-channel slab outer, taps inner
                      __builtin_amdgcn_sched_barrier(0);
-                     wload(std::integral_constant<int, STEP_B + s + 2>{});
+                     wload(IC<STEP_B + s + 2>{});
                      [&]<int... Ks>(std::integer_sequence<int, Ks...>) {
                          (([&] {
                               constexpr int i = 4 * s + Ks;
-                              if constexpr (i + 1 < 72) bread(std::integral_constant<int, i + 1>{});
+                              if constexpr (i + 1 < 72) bread(IC<i + 1>{});
                               __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                               for (int j = 0; j < 2; ++j) acc[j] = Half<H>::mfma32(wr[(STEP_B + s) % 3][Ks], bv[i & 1][j], acc[j]);
@@ -270,10 +261,7 @@ __global__ __launch_bounds__(NTHR, 1) void res_chain_kernel(ResArgs a) {
                     const int c0 = 32 * cb + 8 * q + 4 * h;
                     const float4 sc = *reinterpret_cast<const float4*>(s_ss + 2 * RC_MID + c0);
                     const float4 sh = *reinterpret_cast<const float4*>(s_ss + 3 * RC_MID + c0);
-                    uint2 o;
-                    o.x = Half<H>::pack2_relu(fmaf(acc[j][4 * q], sc.x, sh.x), fmaf(acc[j][4 * q + 1], sc.y, sh.y));
-                    o.y = Half<H>::pack2_relu(fmaf(acc[j][4 * q + 2], sc.z, sh.z), fmaf(acc[j][4 * q + 3], sc.w, sh.w));
-                    *reinterpret_cast<uint2*>(s_y2 + (64 * pg + 32 * j + l32) * YPITCH + c0 * 2) = o;
+                    *reinterpret_cast<uint2*>(s_y2 + (64 * pg + 32 * j + l32) * YPITCH + c0 * 2) = bn_relu4<H>(acc[j], q, sc, sh);
                 }
         }
         storeC(I0{}, 0);                                                          // x chunk 0 of the tile's pixels (requested at the end of phase A)
@@ -291,7 +279,7 @@ __global__ __launch_bounds__(NTHR, 1) void res_chain_kernel(ResArgs a) {
                 (([&] {
                      constexpr int s = Ss;                                        // chunk of the dual GEMM: 0, 1 = y2; 2 .. 9 = x chunk s - 2
                      __builtin_amdgcn_sched_barrier(0);
-                     wload(std::integral_constant<int, STEP_C + s + 2>{});
+                     wload(IC<STEP_C + s + 2>{});
                      const char* bp = s < 2 ? s_y2 + l32 * YPITCH + s * 128 + 64 * h : s_x[s & 1] + l32 * XPITCH + 64 * h;
                      constexpr int pitch = s < 2 ? YPITCH : XPITCH;
                      uint4 bv[2][4];
@@ -308,8 +296,8 @@ __global__ __launch_bounds__(NTHR, 1) void res_chain_kernel(ResArgs a) {
                          for (int j = 0; j < 4; ++j) acc[j] = Half<H>::mfma32(wr[(STEP_C + s) % 3][ks], bv[ks & 1][j], acc[j]);
                      }
                      if constexpr (s >= 2 && s < 9) {                             // x chunk s - 1 -> buffer (s + 1) & 1 (free since the last barrier); s + 1 on its way
-                         storeC(std::integral_constant<int, (s + 1) & 1>{}, (s + 1) & 1);
-                         if constexpr (s + 1 < 8) loadC(std::integral_constant<int, (s + 1) & 1>{}, s + 1);
+                         storeC(IC<(s + 1) & 1>{}, (s + 1) & 1);
+                         if constexpr (s + 1 < 8) loadC(IC<(s + 1) & 1>{}, s + 1);
                          __syncthreads();
                      }
                  }()),
@@ -369,12 +357,7 @@ extern "C" int dir_residual_chain_forward(const dir_res_chain_params* p, const v
     a.pre_sc = p->pre_scale; a.pre_sh = p->pre_shift; a.sc1 = p->scale1; a.sh1 = p->shift1; a.sc2 = p->scale2; a.sh2 = p->shift2; a.sh3 = p->shift3;
     a.B = B; a.H = H; a.W = W; a.in_cs = in_cstride; a.in_co = in_coff; a.out_cs = out_cstride; a.out_co = out_coff;
     a.tiles_x = W / TW; a.tiles_y = H / TH; a.ntiles = B * a.tiles_x * a.tiles_y;
-    static int num_cu = 0;
-    if (!num_cu) {
-        int dev = 0; hipDeviceProp_t pr;
-        num_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256;
-    }
-    const int grid = a.ntiles < num_cu ? a.ntiles : num_cu;
+    const int grid = persistent_grid(a.ntiles);
     hipStream_t s = (hipStream_t)stream;
     if (p->dtype == DIR_DT_F16) DIR_LAUNCH((res_chain_kernel<f16s_t>), dim3(grid), dim3(NTHR), 0, s, a);
     else DIR_LAUNCH((res_chain_kernel<bf16_t>), dim3(grid), dim3(NTHR), 0, s, a);

@@ -265,12 +265,7 @@ extern "C" int dir_stem_pool_forward_dt(const void* img, int img_dtype, int out_
             a.nm.mean[c] = mean_host[c]; a.nm.stdv[c] = std_host[c];
         }
     }
-    static int num_cu = 0;
-    if (!num_cu) {
-        int dev = 0; hipDeviceProp_t p;
-        num_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) ? p.multiProcessorCount : 256;
-    }
-    const int grid = (int)(nt < 2ll * num_cu ? nt : 2ll * num_cu);
+    const int grid = dir::persistent_grid(nt, 2);
     hipStream_t s = (hipStream_t)stream;
     a.stamps = dir::stamps_begin("stem");
     if (out_dtype == DIR_DT_F16) {

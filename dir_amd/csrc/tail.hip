@@ -11,7 +11,7 @@
 // GEMMs are computed as D[channel][pixel] (weights = MFMA A operand): a lane holds 4 consecutive channels of a pixel -- what the
 // bf16 NHWC stores, the residual loads and the LDS hand-over between the GEMMs want (bneck.hip).  The weights do not fit on the
 // CU (w3 + w1n = 256 KB at layer2, 1 MB at layer3): every wave STREAMS its own slice from L2 into a register ring, fragment by
-// fragment, in exactly the order its MFMAs consume them -- the host packs them in that order (dir_amd/engine.py::pack_tail_stream),
+// fragment, in exactly the order its MFMAs consume them -- the host packs them in that order (dir_amd/packing.py::pack_tail_stream),
 // so a fragment is one coalesced 1 KB load per wave and no weight byte goes through LDS.  The block output is processed in
 // 512-channel halves (NH = C4 / 512) so that the T tile ([64 px][512 ch] bf16, 65 KB) fits in LDS at layer3 too; the next conv1
 // accumulates over the halves in registers.  Per unit (tile, half):
@@ -21,38 +21,18 @@
 //   C. next conv1: T (LDS) x this wave's N2 / 8 output channels (stream), accumulated over the halves; after the last half
 //      bn1 + ReLU -> y1n (HBM)
 // The next tile's y2 rows are requested at the top of a tile and parked in LDS at its end.
-#include "conv_common.h"
+#include "chain_common.h"
 
 namespace dir {
 namespace {
 
-using convk::bf16_t;
+using namespace chain;
 using convk::f16s_t;
-using convk::f32x16;
-using convk::Half;
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 
-// The activations are touched once per launch; the weight stream is re-read by every workgroup.  DIR_TAIL_NT (compile-time A/B
-// switch) marks the residual loads and block-output stores non-temporal so that they do not push the weights out of L2.
-// MEASURED AND REJECTED (r02): 46.6 -> 71.0 us at layer2, 34.7 -> 44.6 us at layer3 -- the tensors a layer reads were written by the
-// previous launch and sit in the 256 MB Infinity Cache; a non-temporal access gives that up.  Off.
-#ifndef DIR_TAIL_RES16
-#define DIR_TAIL_RES16 1
-#endif
-#ifndef DIR_TAIL_NT
-#define DIR_TAIL_NT 0
-#endif
-#if DIR_TAIL_NT
-typedef unsigned __attribute__((ext_vector_type(2))) u32x2_t;
-typedef unsigned __attribute__((ext_vector_type(4))) u32x4_t;
-__device__ __forceinline__ uint2 nt_load2(const uint2* p) { const u32x2_t v = __builtin_nontemporal_load(reinterpret_cast<const u32x2_t*>(p)); return make_uint2(v.x, v.y); }
-__device__ __forceinline__ void nt_store4(uint4 v, uint4* p) { __builtin_nontemporal_store(u32x4_t{v.x, v.y, v.z, v.w}, reinterpret_cast<u32x4_t*>(p)); }
-#define NT_LOAD(p) nt_load2(p)
-#define NT_STORE(v, p) nt_store4(v, p)
-#else
-#define NT_LOAD(p) (*(p))
-#define NT_STORE(v, p) (*(p) = (v))
-#endif
+// The activations are touched once per launch; the weight stream is re-read by every workgroup.  Non-temporal residual loads and block-output
+// stores (so that they do not push the weights out of L2): MEASURED AND REJECTED (r02): 46.6 -> 71.0 us at layer2, 34.7 -> 44.6 us at layer3 --
+// the tensors a layer reads were written by the previous launch and sit in the 256 MB Infinity Cache; a non-temporal access gives that up.
 
 constexpr int TM = 64;                 // pixels per tile
 constexpr int HC = 512;                // channels per half of the block output
@@ -65,11 +45,6 @@ struct TailArgs {
     const float* sc3; const float* sh3; const float* sc1n; const float* sh1n;
     int ntiles; unsigned y2_bytes;
 };
-
-template <typename H> __device__ __forceinline__ void unpack4(uint2 v, float (&f)[4]) {
-    convk::unpack2<H>(v.x, f[0], f[1]);
-    convk::unpack2<H>(v.y, f[2], f[3]);
-}
 
 // P: planes (K of conv3); N2: output channels of the next conv1 (128: 16 per wave on v_mfma_f32_16x16x32_bf16; 256: 32 per wave
 // on v_mfma_f32_32x32x16_bf16)
@@ -113,33 +88,16 @@ __global__ __launch_bounds__(NTHR, 1) void tail_chain_kernel(TailArgs a) {
             convk::lds_dma16_m0(yd, y2_lds + buf * (TM * YROW) + (8 * i + wave) * 1024, voff, 0);
         }
     };
-    // ---- residual of a unit in the epilogue-B layout: pixel 32 pb + l32, channels half*512 + 64 wave + 32 cb + 8 q + 4 h .. +4
-#if DIR_TAIL_RES16
-    // fetched as 16-byte chunks -- lane half h takes channels 16 j + 8 h .. + 8 of each 32-channel block -- and turned into the accumulator
-    // layout at the point of use by swapping 8 bytes per chunk with the partner lane (v_permlane32_swap): half the load instructions,
-    // 32 contiguous bytes per pixel row and instruction instead of 16
+    // ---- residual of a unit (pixel 32 pb + l32, channels half*512 + 64 wave + 32 cb ..) as 16-byte chunks, turned into the epilogue-B layout
+    //      where it is used (chain_common.h: res16_fetch / res16_take)
     uint4 xr[2][2][2];
     auto res_fetch = [&](int tile, int half) {
 #pragma unroll
         for (int pb = 0; pb < 2; ++pb) {
             const bf16_t* rp = a.res + ((long long)tile * TM + 32 * pb + l32) * C4 + half * HC + 64 * wave + 8 * h;
 #pragma unroll
-            for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) xr[cb][pb][j] = *reinterpret_cast<const uint4*>(rp + 32 * cb + 16 * j);
+            for (int cb = 0; cb < 2; ++cb) res16_fetch(rp + 32 * cb, xr[cb][pb]);
         }
-#else
-    uint2 xr[2][2][4];
-    auto res_fetch = [&](int tile, int half) {
-#pragma unroll
-        for (int pb = 0; pb < 2; ++pb) {
-            const bf16_t* rp = a.res + ((long long)tile * TM + 32 * pb + l32) * C4 + half * HC + 64 * wave + 4 * h;
-#pragma unroll
-            for (int cb = 0; cb < 2; ++cb)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) xr[cb][pb][q] = NT_LOAD(reinterpret_cast<const uint2*>(rp + 32 * cb + 8 * q));
-        }
-#endif
     };
     // ---- weight stream of this wave: fragment f of half hf at wstream[((hf * 8 + wave) * NF + f) * 64 + lane]
     uint4 ring[2][GRP];
@@ -151,7 +109,7 @@ __global__ __launch_bounds__(NTHR, 1) void tail_chain_kernel(TailArgs a) {
     };
 
     y2_dma(t, 0);
-    ring_load(std::integral_constant<int, 0>{}, 0, 0);
+    ring_load(IC<0>{}, 0, 0);
     res_fetch(t, 0);
     convk::wait_vmcnt<0>();
     __syncthreads();
@@ -201,18 +159,18 @@ __global__ __launch_bounds__(NTHR, 1) void tail_chain_kernel(TailArgs a) {
                         for (int r = 0; r < 16; ++r) accc32[pb][r] = 0.f;
                 }
             }
-            act_read(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+            act_read(IC<0>{}, IC<0>{});
             // the unit's fragments, group by group; the next group (of this unit, or group 0 of the next unit) is requested first
             [&]<int... G>(std::integer_sequence<int, G...>) {
                 (([&] {
                      constexpr int grp = G, slot = G & 1;
-                     if constexpr (grp + 1 < NG) ring_load(std::integral_constant<int, slot ^ 1>{}, hf, grp + 1);
-                     else ring_load(std::integral_constant<int, slot ^ 1>{}, last_half ? 0 : hf + 1, 0);     // NG is even: slot 0 again
+                     if constexpr (grp + 1 < NG) ring_load(IC<slot ^ 1>{}, hf, grp + 1);
+                     else ring_load(IC<slot ^ 1>{}, last_half ? 0 : hf + 1, 0);     // NG is even: slot 0 again
                      [&]<int... I>(std::integer_sequence<int, I...>) {
                          (([&] {
                               constexpr int f = grp * GRP + I, set = f & 1;
                               // operands of the next step (not across the phase boundary: T does not exist yet; not across the unit)
-                              if constexpr (f + 1 < NF && f + 1 != NBF) act_read(std::integral_constant<int, f + 1>{}, std::integral_constant<int, set ^ 1>{});
+                              if constexpr (f + 1 < NF && f + 1 != NBF) act_read(IC<f + 1>{}, IC<set ^ 1>{});
                               if constexpr (f < NBF) {
                                   // ---- B. conv3: fragment (channel block cb, k-step ks), channel-block-major: two accumulators live
                                   constexpr int cb = f / KBS, ks = f - cb * KBS;
@@ -226,51 +184,16 @@ __global__ __launch_bounds__(NTHR, 1) void tail_chain_kernel(TailArgs a) {
                                   for (int pb = 0; pb < 2; ++pb)
                                       accb[pb] = Half<H>::mfma32(ring[slot][I], bop[set][pb], accb[pb]);
                                   if constexpr (ks == KBS - 1) {
-                                      // ---- epilogue B of this channel block -> T: bn3 + residual + ReLU, bf16
-#pragma unroll
-                                      for (int q = 0; q < 4; ++q) {
-                                          const int cl = 64 * wave + 32 * cb + 8 * q + 4 * h;                  // channel inside the half
-                                          const float4 sc = *reinterpret_cast<const float4*>(s_ss + hf * HC + cl);
-                                          const float4 sh = *reinterpret_cast<const float4*>(s_ss + C4 + hf * HC + cl);
-#pragma unroll
-                                          for (int pb = 0; pb < 2; ++pb) {
-                                              float v[4] = {fmaf(accb[pb][4 * q], sc.x, sh.x), fmaf(accb[pb][4 * q + 1], sc.y, sh.y),
-                                                            fmaf(accb[pb][4 * q + 2], sc.z, sh.z), fmaf(accb[pb][4 * q + 3], sc.w, sh.w)};
-                                              float rv[4];
-#if DIR_TAIL_RES16
-                                              {   // (q even, q odd) = swap(lower 8 bytes, upper 8 bytes) of chunk q / 2, dword by dword
-                                                  const uint4 c = xr[cb][pb][q >> 1];
-                                                  const auto sx = __builtin_amdgcn_permlane32_swap(c.x, c.z, false, false);
-                                                  const auto sy = __builtin_amdgcn_permlane32_swap(c.y, c.w, false, false);
-                                                  unpack4<H>(make_uint2(sx[q & 1], sy[q & 1]), rv);
-                                              }
-#else
-                                              unpack4<H>(xr[cb][pb][q], rv);
-#endif
-#pragma unroll
-                                              for (int e = 0; e < 4; ++e) v[e] += rv[e];
-                                              uint2 o;
-                                              o.x = Half<H>::pack2_relu(v[0], v[1]);
-                                              o.y = Half<H>::pack2_relu(v[2], v[3]);
-                                              *reinterpret_cast<uint2*>(s_t + (32 * pb + l32) * TPITCH + cl * 2) = o;
-                                          }
-                                          __builtin_amdgcn_sched_barrier(0);          // keep the (sc, sh) reads of later q's out of this one's registers
-                                      }
+                                      // ---- epilogue B of this channel block -> T: bn3 + residual + ReLU, rounded
+                                      epilogue_b<H, TPITCH>(accb, xr[cb], s_ss + hf * HC, s_ss + C4 + hf * HC, s_t, 64 * wave + 32 * cb, l32, h);
                                   }
                                   if constexpr (f == NBF - 1) {
                                       __syncthreads();                               // T = this half of the block output; every wave is done with y2
-                                      act_read(std::integral_constant<int, NBF>{}, std::integral_constant<int, set ^ 1>{});
+                                      act_read(IC<NBF>{}, IC<set ^ 1>{});
                                       // residual of the NEXT unit into the registers just consumed (a unit of lead time)
                                       if (!last_half) res_fetch(t, hf + 1);
                                       else if (more) res_fetch(t + tstep, 0);
-                                      // block output: coalesced 16-byte stores from T (chunk c = pixel c >> 6, 16-byte chunk c & 63)
-#pragma unroll
-                                      for (int i = 0; i < TM * (HC / 8) / NTHR; ++i) {
-                                          const int c = tid + NTHR * i;
-                                          NT_STORE(*reinterpret_cast<const uint4*>(s_t + (c >> 6) * TPITCH + (c & 63) * 16),
-                                                   reinterpret_cast<uint4*>(a.out + ((long long)t * TM + (c >> 6)) * C4 + hf * HC + (c & 63) * 8));
-                                          if (i & 1) __builtin_amdgcn_sched_barrier(0);
-                                      }
+                                      store_t_to_out<NTHR, TM, HC, TPITCH>(s_t, a.out, C4, t, hf, tid);
                                   }
                               } else {
                                   // ---- C. next conv1 over this half's 512 input channels
@@ -301,12 +224,8 @@ __global__ __launch_bounds__(NTHR, 1) void tail_chain_kernel(TailArgs a) {
                     const float4 sc = *reinterpret_cast<const float4*>(s_ss + 2 * C4 + c0);
                     const float4 sh = *reinterpret_cast<const float4*>(s_ss + 2 * C4 + N2 + c0);
 #pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        uint2 o;
-                        o.x = Half<H>::pack2_relu(fmaf(accc16[u][0], sc.x, sh.x), fmaf(accc16[u][1], sc.y, sh.y));
-                        o.y = Half<H>::pack2_relu(fmaf(accc16[u][2], sc.z, sh.z), fmaf(accc16[u][3], sc.w, sh.w));
-                        *reinterpret_cast<uint2*>(a.y1n + ((long long)t * TM + 16 * u + l16) * N2 + c0) = o;
-                    }
+                    for (int u = 0; u < 4; ++u)
+                        *reinterpret_cast<uint2*>(a.y1n + ((long long)t * TM + 16 * u + l16) * N2 + c0) = bn_relu4<H>(accc16[u], 0, sc, sh);
                 } else {
 #pragma unroll
                     for (int pb = 0; pb < 2; ++pb) {
@@ -316,22 +235,9 @@ __global__ __launch_bounds__(NTHR, 1) void tail_chain_kernel(TailArgs a) {
                             const int c0 = 32 * wave + 8 * q + 4 * h;
                             const float4 sc = *reinterpret_cast<const float4*>(s_ss + 2 * C4 + c0);
                             const float4 sh = *reinterpret_cast<const float4*>(s_ss + 2 * C4 + N2 + c0);
-                            o[q].x = Half<H>::pack2_relu(fmaf(accc32[pb][4 * q], sc.x, sh.x), fmaf(accc32[pb][4 * q + 1], sc.y, sh.y));
-                            o[q].y = Half<H>::pack2_relu(fmaf(accc32[pb][4 * q + 2], sc.z, sh.z), fmaf(accc32[pb][4 * q + 3], sc.w, sh.w));
+                            o[q] = bn_relu4<H>(accc32[pb], q, sc, sh);
                         }
-#if DIR_TAIL_RES16
-                        // the residual fetch's swap in reverse: lane half h ends up with channels 16 j + 8 h .. + 8 -- one 16-byte store per j
-#pragma unroll
-                        for (int j = 0; j < 2; ++j) {
-                            const auto dx = __builtin_amdgcn_permlane32_swap(o[2 * j].x, o[2 * j + 1].x, false, false);
-                            const auto dy = __builtin_amdgcn_permlane32_swap(o[2 * j].y, o[2 * j + 1].y, false, false);
-                            *reinterpret_cast<uint4*>(a.y1n + ((long long)t * TM + 32 * pb + l32) * N2 + 32 * wave + 16 * j + 8 * h) = make_uint4(dx[0], dy[0], dx[1], dy[1]);
-                        }
-#else
-#pragma unroll
-                        for (int q = 0; q < 4; ++q)
-                            *reinterpret_cast<uint2*>(a.y1n + ((long long)t * TM + 32 * pb + l32) * N2 + 32 * wave + 8 * q + 4 * h) = o[q];
-#endif
+                        store16_swapped(o, a.y1n + ((long long)t * TM + 32 * pb + l32) * N2 + 32 * wave + 8 * h);
                     }
                 }
             }
@@ -347,7 +253,7 @@ __global__ __launch_bounds__(NTHR, 1) void tail_chain_kernel(TailArgs a) {
 // above has nothing to overlap its own latencies with): 4 waves, 32-pixel tiles, <= 76 KB of LDS -- TWO workgroups per CU, each
 // in a different phase.  Same phases and arithmetic; a wave owns 128 conv3 channels per half (4 blocks, one accumulator live at a
 // time) and N2 / 4 channels of the next conv1 on v_mfma_f32_32x32x16_bf16.  The weight stream is packed for 4 waves
-// (dir_amd/engine.py::pack_tail_stream(..., waves=4)).
+// (dir_amd/packing.py::pack_tail_stream(..., waves=4)).
 constexpr int TTM = 32, TTHR = 256;
 
 template <int P, int N2, typename H = bf16_t>
@@ -393,7 +299,7 @@ __global__ __launch_bounds__(TTHR, 2) void tail_thin_kernel(TailArgs a) {
 #pragma unroll
         for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
-            for (int q = 0; q < 4; ++q) xr[cb][q] = NT_LOAD(reinterpret_cast<const uint2*>(rp + 32 * cb + 8 * q));
+            for (int q = 0; q < 4; ++q) xr[cb][q] = *reinterpret_cast<const uint2*>(rp + 32 * cb + 8 * q);
     };
     uint4 ring[2][GRP];
     auto ring_load = [&](auto Slot, int hf, int grp) {
@@ -404,7 +310,7 @@ __global__ __launch_bounds__(TTHR, 2) void tail_thin_kernel(TailArgs a) {
     };
 
     y2_dma(t, 0);
-    ring_load(std::integral_constant<int, 0>{}, 0, 0);
+    ring_load(IC<0>{}, 0, 0);
     res_fetch(t, 0);
     convk::wait_vmcnt<0>();
     __syncthreads();
@@ -438,12 +344,12 @@ __global__ __launch_bounds__(TTHR, 2) void tail_thin_kernel(TailArgs a) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) accc[cc][r] = 0.f;
             }
-            act_read(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
+            act_read(IC<0>{}, IC<0>{});
             [&]<int... G>(std::integer_sequence<int, G...>) {
                 (([&] {
                      constexpr int grp = G, slot = G & 1;
-                     if constexpr (grp + 1 < NG) ring_load(std::integral_constant<int, slot ^ 1>{}, hf, grp + 1);
-                     else ring_load(std::integral_constant<int, slot ^ 1>{}, last_half ? 0 : hf + 1, 0);
+                     if constexpr (grp + 1 < NG) ring_load(IC<slot ^ 1>{}, hf, grp + 1);
+                     else ring_load(IC<slot ^ 1>{}, last_half ? 0 : hf + 1, 0);
                      [&]<int... I>(std::integer_sequence<int, I...>) {
                          (([&] {
                               constexpr int f = grp * GRP + I;
@@ -452,7 +358,7 @@ __global__ __launch_bounds__(TTHR, 2) void tail_thin_kernel(TailArgs a) {
                               constexpr bool same_next = f >= NBF && f + 1 < NF && (f - NBF) / NCC == (f + 1 - NBF) / NCC;
                               constexpr int set = f < NBF ? (f & 1) : ((((f - NBF) / NCC) + NBF) & 1);
                               if constexpr (f + 1 < NF && f + 1 != NBF && !same_next)
-                                  act_read(std::integral_constant<int, f + 1>{}, std::integral_constant<int, set ^ 1>{});
+                                  act_read(IC<f + 1>{}, IC<set ^ 1>{});
                               if constexpr (f < NBF) {
                                   constexpr int cb = f / KBS, ks = f - cb * KBS;
                                   if constexpr (ks == 0) {
@@ -466,30 +372,18 @@ __global__ __launch_bounds__(TTHR, 2) void tail_thin_kernel(TailArgs a) {
                                           const int cl = 128 * wave + 32 * cb + 8 * q + 4 * h;
                                           const float4 sc = *reinterpret_cast<const float4*>(s_ss + hf * HC + cl);
                                           const float4 sh = *reinterpret_cast<const float4*>(s_ss + C4 + hf * HC + cl);
-                                          float v[4] = {fmaf(accb[4 * q], sc.x, sh.x), fmaf(accb[4 * q + 1], sc.y, sh.y),
-                                                        fmaf(accb[4 * q + 2], sc.z, sh.z), fmaf(accb[4 * q + 3], sc.w, sh.w)};
-                                          float rv[4];
+                                          float v[4], rv[4];
+                                          bn4(accb, q, sc, sh, v);
                                           unpack4<H>(xr[cb][q], rv);
-#pragma unroll
-                                          for (int e = 0; e < 4; ++e) v[e] += rv[e];
-                                          uint2 o;
-                                          o.x = Half<H>::pack2_relu(v[0], v[1]);
-                                          o.y = Half<H>::pack2_relu(v[2], v[3]);
-                                          *reinterpret_cast<uint2*>(s_t + l32 * TPITCH + cl * 2) = o;
+                                          *reinterpret_cast<uint2*>(s_t + l32 * TPITCH + cl * 2) = add_relu4<H>(v, rv);
                                       }
                                   }
                                   if constexpr (f == NBF - 1) {
                                       __syncthreads();
-                                      act_read(std::integral_constant<int, NBF>{}, std::integral_constant<int, (NBF & 1)>{});
+                                      act_read(IC<NBF>{}, IC<(NBF & 1)>{});
                                       if (!last_half) res_fetch(t, hf + 1);
                                       else if (more) res_fetch(t + tstep, 0);
-#pragma unroll
-                                      for (int i = 0; i < TTM * (HC / 8) / TTHR; ++i) {
-                                          const int c = tid + TTHR * i;
-                                          NT_STORE(*reinterpret_cast<const uint4*>(s_t + (c >> 6) * TPITCH + (c & 63) * 16),
-                                                   reinterpret_cast<uint4*>(a.out + ((long long)t * TTM + (c >> 6)) * C4 + hf * HC + (c & 63) * 8));
-                                          if (i & 1) __builtin_amdgcn_sched_barrier(0);
-                                      }
+                                      store_t_to_out<TTHR, TTM, HC, TPITCH>(s_t, a.out, C4, t, hf, tid);
                                   }
                               } else {
                                   constexpr int cc = (f - NBF) % NCC;
@@ -511,10 +405,7 @@ __global__ __launch_bounds__(TTHR, 2) void tail_thin_kernel(TailArgs a) {
                         const int c0 = (N2 / 4) * wave + 32 * cc + 8 * q + 4 * h;
                         const float4 sc = *reinterpret_cast<const float4*>(s_ss + 2 * C4 + c0);
                         const float4 sh = *reinterpret_cast<const float4*>(s_ss + 2 * C4 + N2 + c0);
-                        uint2 o;
-                        o.x = Half<H>::pack2_relu(fmaf(accc[cc][4 * q], sc.x, sh.x), fmaf(accc[cc][4 * q + 1], sc.y, sh.y));
-                        o.y = Half<H>::pack2_relu(fmaf(accc[cc][4 * q + 2], sc.z, sh.z), fmaf(accc[cc][4 * q + 3], sc.w, sh.w));
-                        *reinterpret_cast<uint2*>(a.y1n + ((long long)t * TTM + l32) * N2 + c0) = o;
+                        *reinterpret_cast<uint2*>(a.y1n + ((long long)t * TTM + l32) * N2 + c0) = bn_relu4<H>(accc[cc], q, sc, sh);
                     }
             }
             __syncthreads();
@@ -541,15 +432,10 @@ extern "C" int dir_bottleneck_tail_forward(const dir_bneck_tail_params* p, const
     a.ntiles = (int)(M / TM);
     DIR_REQUIRE(M * p->planes * 2 < (1ll << 31), "dir_bottleneck_tail_forward: y2 must be < 2 GiB (32-bit buffer offsets)");
     a.y2_bytes = (unsigned)(M * p->planes * 2);
-    static int num_cu = 0;
-    if (!num_cu) {
-        int dev = 0; hipDeviceProp_t pr;
-        num_cu = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&pr, dev) == hipSuccess) ? pr.multiProcessorCount : 256;
-    }
     hipStream_t s = (hipStream_t)stream;
     if (p->waves == 4) {               // thin variant: 32-pixel tiles, two workgroups per CU
         a.ntiles = (int)(M / TTM);
-        const int grid4 = a.ntiles < 2 * num_cu ? a.ntiles : 2 * num_cu;
+        const int grid4 = persistent_grid(a.ntiles, 2);
 #define DIR_TAIL4(P_, N2_) do { if (f16) DIR_LAUNCH((tail_thin_kernel<P_, N2_, f16s_t>), dim3(grid4), dim3(TTHR), 0, s, a); \
                                  else DIR_LAUNCH((tail_thin_kernel<P_, N2_, bf16_t>), dim3(grid4), dim3(TTHR), 0, s, a); } while (0)
         if (p->planes == 128 && p->n_next == 128) DIR_TAIL4(128, 128);
@@ -559,7 +445,7 @@ extern "C" int dir_bottleneck_tail_forward(const dir_bneck_tail_params* p, const
 #undef DIR_TAIL4
         return check_launch("dir_bottleneck_tail_forward");
     }
-    const int grid = a.ntiles < num_cu ? a.ntiles : num_cu;
+    const int grid = persistent_grid(a.ntiles);
 #define DIR_TAIL(P_, N2_) do { if (f16) DIR_LAUNCH((tail_chain_kernel<P_, N2_, f16s_t>), dim3(grid), dim3(NTHR), 0, s, a); \
                                 else DIR_LAUNCH((tail_chain_kernel<P_, N2_, bf16_t>), dim3(grid), dim3(NTHR), 0, s, a); } while (0)
     if (p->planes == 128 && p->n_next == 128) DIR_TAIL(128, 128);

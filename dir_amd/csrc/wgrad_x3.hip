@@ -255,13 +255,9 @@ int x3_tile(int c) { return c > 64 ? 128 : 64; }
 template <int TM, int TN>
 int x3_slots_of() {
     static const int slots = []() {
-        int dev = 0, cus = 256, occ = 2;
-        if (hipGetDevice(&dev) == hipSuccess) {
-            hipDeviceProp_t pr;
-            if (hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0) cus = pr.multiProcessorCount;
-        }
+        int occ = 2;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, conv_wgrad_x3_kernel<TM, TN, 4>, 256, 0) != hipSuccess || occ < 1) occ = 2;
-        return cus * occ;
+        return dir::num_cus() * occ;
     }();
     return slots;
 }
